@@ -6,15 +6,18 @@ One step = one full training step exactly as train.py:55-74 does it -- DeepSet +
 4 GINE layers (HIP engine) + head + PostProcess + MixedLoss + backward + AdamW -- on one
 pre-collated batch resident in HBM.  N=1 runs configs[1] (500-station k=10 graphs, 32 per
 GPU); with N>1 every rank runs its own 32 graphs (weak scaling) and the gradient is
-averaged with one RCCL all-reduce per step, captured in the step's HIP graph.  The same run
-also measures cfg4 (global batch 256 split over the N ranks: strong scaling) and reports
-it as ``strong_scaling_cfg4``.
+averaged with one RCCL all-reduce per step, captured in the step's HIP graph.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--dump-outputs DIR]
+    python bench.py --full [...]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  Per-kernel timings (HIP events on the launch stream) and the
-CPU baseline (oracle, rank 0, N=1 only) are measured in the same process.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints
+the line; ``--dump-outputs DIR`` also writes what the last timed step computed as
+``DIR/<name>.npy``.  ``--full`` adds, in the same process, everything else the line can
+carry: cfg4 (global batch 256 split over the N ranks: strong scaling, reported as
+``strong_scaling_cfg4``), the per-kernel timings (HIP events on the launch stream) with the
+rooflines and the measured copy ceiling, and the CPU baseline (oracle, rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -68,13 +71,23 @@ def parse():
                     help="gnn_hidden override (the D=64 sweep of BASELINE.md:47 / the north "
                          "star's 64-dim features); default: params.json's 128")
     ap.add_argument("--no-graph", action="store_true", help="eager steps (no HIP graph)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the cfg4 strong-scaling line, "
+                         "the per-kernel timings with the rooflines and the copy ceiling, "
+                         "and the CPU baseline (each has a --no-* / size option below); "
+                         "without it the line holds null for them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed -- loss, "
+                         "predictions, gradients and the updated parameters -- as float32 "
+                         "DIR/<name>.npy (rank 0; same arguments, same inputs, every run)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target duration of the CPU-baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--kernel-reps", type=int, default=50)
+                    help="--full: target duration of the CPU-baseline sample")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--kernel-reps", type=int, default=50,
+                    help="--full: launches per timed kernel")
     ap.add_argument("--no-strong", action="store_true",
-                    help="skip the cfg4 strong-scaling line (global batch 256) that the "
-                         "default cfg2 run adds")
+                    help="--full without the cfg4 strong-scaling line (global batch 256) "
+                         "that a cfg2 run adds")
     ap.add_argument("--allreduce", choices=("graph", "split"), default="split",
                     help="split (default): fwd+bwd graph, the RCCL all-reduce launched "
                          "between it and the optimizer graph -- keeps multi-rank runs off "
@@ -120,9 +133,12 @@ def parse():
 # -----------------------------------------------------------------------------------------
 class Trainer:
     def __init__(self, cfg, device, rank, world, graphs_per_rank, allreduce="graph",
-                 force_allreduce=False, station_order="locality"):
+                 force_allreduce=False, station_order="locality", keep_pred=False):
         self.cfg, self.device, self.world = cfg, device, world
         self.allreduce = allreduce
+        # --dump-outputs: the step's predictions stay referenced (in a captured step their
+        # memory is then the graph's for good, and holds the last replay's values)
+        self.keep_pred, self.pred = keep_pred, None
         self.collective = world > 1 or force_allreduce
         params = cfg.params()
         self.params = params
@@ -159,6 +175,8 @@ class Trainer:
     def fwd_bwd(self):
         self.opt.zero_grad()            # set_to_none: kernels write grads into flat slices
         pred = self.model(self.batch)
+        if self.keep_pred:
+            self.pred = pred.detach()
         loss = self.model.loss_fn.crps(pred, self.batch.y)
         gradbuf.loss_backward(loss)      # (no seed-fill launch)
         self.opt.gather_grads()         # flat_grad complete before the all-reduce
@@ -209,7 +227,14 @@ class Trainer:
 
     def step(self):
         if self.graph_fb is None:
-            return self.eager_step()
+            loss = self.eager_step()
+            if self.keep_pred:
+                # --dump-outputs of --no-graph steps.  Detached, and only here, never in the
+                # eager warm-up before a capture: a held loss keeps its step's autograd graph
+                # alive, and AccumulateGrad nodes of the warm-up's stream inside a capture on
+                # another stream end the process
+                self.loss = loss.detach()
+            return loss
         timed = self.ar_events is not None and self.collective and self.graph_opt is not None
         if timed:
             stream = torch.cuda.current_stream(self.device)
@@ -744,11 +769,35 @@ def cpu_baseline(cfg, graphs, seconds):
 
 
 # -----------------------------------------------------------------------------------------
-def measure(cfg, graphs_per_rank, args, device, rank, world):
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+
+
+def dump_outputs(tr: Trainer, out_dir: str) -> dict:
+    """What a caller of the timed step holds after the last one, as float32 ``<name>.npy``:
+    the loss, the predictions, the flat gradient buffer (after the all-reduce) and the
+    updated flat parameter buffer (FlatAdamW's layout: parameters() order, 64-float
+    aligned, gaps zero).  An array over its share of the size limit is written as a fixed
+    seeded sample of its elements.  Returns {name: shape}."""
+    import numpy as np
+    arrays = {"loss": tr.loss, "predictions": tr.pred, "gradients": tr.opt.flat_grad,
+              "parameters": tr.opt.flat_param}
+    share = DUMP_LIMIT_BYTES // len(arrays) // 4
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def measure(cfg, graphs_per_rank, args, device, rank, world, keep_pred=False):
     """Build the trainer, warm up, capture, then time ``args.steps`` steps between barriers
     + synchronisations; returns (trainer, max-over-ranks seconds, HIP-event percentiles)."""
     tr = Trainer(cfg, device, rank, world, graphs_per_rank, args.allreduce,
-                 args.force_allreduce, args.station_order)
+                 args.force_allreduce, args.station_order, keep_pred)
     side = torch.cuda.Stream(device)
     side.wait_stream(torch.cuda.current_stream(device))
     with torch.cuda.stream(side):
@@ -1167,6 +1216,9 @@ def main():
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world) or world)
     threads = max(1, cpu_share() // max(1, local_world))
     torch.set_num_threads(threads)
+    if args.dump_outputs and (args.dry_run or args.dropin):
+        raise SystemExit("--dump-outputs writes the training step's outputs; --dry-run has "
+                         "none and --dropin times another path")
     if args.dry_run:
         return dry_run(args, rank, world)
     if world > 1 or args.force_allreduce:
@@ -1199,7 +1251,11 @@ def main():
     else:
         graphs_per_rank = cfg.graphs_per_gpu
         scaling = "weak"
-    tr, elapsed, pct = measure(cfg, graphs_per_rank, args, device, rank, world)
+    tr, elapsed, pct = measure(cfg, graphs_per_rank, args, device, rank, world,
+                               keep_pred=bool(args.dump_outputs))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(tr, args.dump_outputs)
     # flag MALL residency when the step's working set is under the 256 MB
     # Infinity Cache -- the peak of live device allocations over the measured steps (inputs,
     # parameters, saved activations, workspaces) is the working-set bound used here
@@ -1215,7 +1271,7 @@ def main():
     edges_per_s = edges_global * layers * args.steps / elapsed
 
     strong = None
-    if args.config == 2 and not args.no_strong:
+    if args.full and args.config == 2 and not args.no_strong:
         # the same model at a fixed global batch of 256 graphs split over
         # the ranks (strong scaling), measured in the same run as the weak-scaling line
         c4 = BENCH_CONFIGS[4].with_hidden(args.hidden)
@@ -1235,14 +1291,16 @@ def main():
                   and dist.get_backend() == "nccl" else None)
     if world > 1 and args.dist_backend == "nccl":
         assert rccl_world == args.gpus, (rccl_world, args.gpus)
-    kernels = time_kernels(tr, args.kernel_reps) if rank == 0 else {}
+    kernels = time_kernels(tr, args.kernel_reps) if args.full and rank == 0 else None
     result = None
     if rank == 0:
         work = sec8d_work(tr.batch.num_nodes, E_rank, tr.params["gnn_hidden"])
-        roof = roofline_for(kernels, layers, work, cfg.name)
-        roof["working_set_bytes"] = int(working_set)
-        roof["mall_resident"] = bool(working_set < MALL_BYTES)
-        roof_mp = roofline_mp(kernels, layers, work, cfg.name)
+        roof = roof_mp = None
+        if args.full:
+            roof = roofline_for(kernels, layers, work, cfg.name)
+            roof["working_set_bytes"] = int(working_set)
+            roof["mall_resident"] = bool(working_set < MALL_BYTES)
+            roof_mp = roofline_mp(kernels, layers, work, cfg.name)
         if roof_mp is not None:
             copy_gbs = copy_ceiling_gbps(device)
             for r in roof_mp.values():
@@ -1250,7 +1308,7 @@ def main():
                 r["frac_of_measured"] = round(r["achieved"] / copy_gbs, 4)
         roof_step = roofline_step(work, layers, ms)
         cpu = None
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             cpu = cpu_baseline(cfg, graphs_per_rank, args.cpu_seconds)
         result = {
             "metric": "training graphs/s (24h_mixed GNN, full train step)",
@@ -1293,6 +1351,10 @@ def main():
             "strong_scaling_cfg4": strong,
             "cpu_baseline": cpu, "kernels": kernels,
             "final_loss": loss_val,
+            # --full: roofline, roofline_message_passing, strong_scaling_cfg4, cpu_baseline
+            # and kernels are measured (null in a plain run); --dump-outputs: {name: shape}
+            # of the <name>.npy files written
+            "full": args.full, "dumped_outputs": dumped,
         }
         print(json.dumps(result), flush=True)
     if dist.is_initialized():

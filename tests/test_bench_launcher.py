@@ -73,6 +73,23 @@ def test_world_size_must_match_gpus():
     assert "must agree" in p.stderr
 
 
+def test_full_is_opt_in_and_dump_outputs_needs_the_training_step(monkeypatch):
+    """A plain run measures the headline only (``--full`` off by default, the sections it
+    adds still selectable under it); ``--dump-outputs`` has nothing to write in a dry run."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.no_cpu and not args.no_strong and args.dump_outputs == "d"
+    p = _run(["--dry-run", "--dump-outputs", "unused"])
+    assert p.returncode != 0 and "--dump-outputs" in p.stderr
+    assert not os.path.exists(os.path.join(ROOT, "unused"))
+
+
 def test_stalled_steps_decomposition():
     """A stalled step is reported with its fwd+bwd stream time, the host wait for it (gloo)
     and the collective's own times; steps within 10x the median are not."""

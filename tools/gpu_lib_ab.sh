@@ -8,7 +8,7 @@ O=gpurun_out/$1; C=$2; shift 2; mkdir -p $O
 for rep in 1 2; do
   for v in "$@"; do
     if [ $v = main ]; then L=raincast-gnn_amd/raincast_gnn/_native/libgine_hip.so; else L=raincast-gnn_amd/raincast_gnn/_native/var/$v/libgine_hip.so; fi
-    GINE_HIP_LIB=$L timeout -k 10 300 python bench.py --config $C --no-cpu --no-strong --steps ${STEPS:-50} --kernel-reps ${KREPS:-20} ${BENCH_ARGS:-} > $O/c${C}_${v}_$rep.json 2> $O/c${C}_${v}_$rep.err
+    GINE_HIP_LIB=$L timeout -k 10 300 python bench.py --full --config $C --no-cpu --no-strong --steps ${STEPS:-50} --kernel-reps ${KREPS:-20} ${BENCH_ARGS:-} > $O/c${C}_${v}_$rep.json 2> $O/c${C}_${v}_$rep.err
     rc=$?; [ $rc -le 1 ] || { echo "crash-class $rc ($v)"; exit $rc; }
     python - "$O/c${C}_${v}_$rep.json" "$v" <<'PY'
 import json, sys

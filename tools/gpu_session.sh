@@ -41,25 +41,25 @@ for s in $STEPS; do
     kvtests) GINE_HIP_LIB=raincast-gnn_amd/raincast_gnn/_native/var/${LIBVAR}/libgine_hip.so \
             run pytest_k_${LIBVAR} 600 python -u -m pytest tests -m gpu -q -rf -k "${KTESTS:-deepset}" --timeout 120 --timeout-method thread ;;
     smoke) run smoke 150 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
-    benchnc) run bench_nocpu 600 python bench.py --no-cpu ;;
-    bench1) run bench_cfg1 600 python bench.py --config 1 ;;
-    bench64) run bench_cfg2_d64 600 python bench.py --hidden 64 ;;
+    bench) run bench 600 python bench.py --full ;;
+    benchnc) run bench_nocpu 600 python bench.py --full --no-cpu ;;
+    bench1) run bench_cfg1 600 python bench.py --full --config 1 ;;
+    bench64) run bench_cfg2_d64 600 python bench.py --full --hidden 64 ;;
     dropin) run bench_dropin 600 python bench.py --dropin --steps 30 ;;
     dropinprof) run rocprof_dropin 600 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv \
                -d "$OUT/prof_dropin" -o run -- python3 bench.py --dropin --steps 20 --warmup 5 ;;
     prof64) run rocprof_d64 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof64" -o run -- \
                python3 bench.py --hidden 64 --steps 20 --warmup 5 --no-cpu --no-strong ;;
-    bench3) run bench_cfg3 600 python bench.py --config 3 --steps 20 ;;
-    bench5) run bench_cfg5 600 python bench.py --config 5 --steps 20 ;;
+    bench3) run bench_cfg3 600 python bench.py --full --config 3 --steps 20 ;;
+    bench5) run bench_cfg5 600 python bench.py --full --config 5 --steps 20 ;;
     prof)  run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
                python3 bench.py --steps 20 --warmup 5 --no-cpu --no-strong ;;
     pmc)   # PMC_ARGS: bench options of the configuration (e.g. "--config 3"); PMC_NAME: its name
            P=${PMC_NAME:-cfg2}
            run pmc_fetch_$P 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_$P" -o run -- \
-               python3 bench.py --steps 5 --warmup 2 --no-cpu --no-strong --no-graph --kernel-reps 5 ${PMC_ARGS:-}
+               python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-strong --no-graph --kernel-reps 5 ${PMC_ARGS:-}
            run pmc_write_$P 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_$P" -o run -- \
-               python3 bench.py --steps 5 --warmup 2 --no-cpu --no-strong --no-graph --kernel-reps 5 ${PMC_ARGS:-}
+               python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-strong --no-graph --kernel-reps 5 ${PMC_ARGS:-}
            python tools/pmc_summary.py "$OUT"/pmc_fetch_$P/run_counter_collection.csv \
                "$OUT"/pmc_write_$P/run_counter_collection.csv --config $P \
                --tree-hash "$(python -c 'import bench; print(bench.source_tree_hash())')" \
@@ -83,13 +83,13 @@ for m, v in d.items():
 print("same final loss bits:", d["graph"]["final_loss"] == d["split"]["final_loss"])
 PY
            ;;
-    dist2) run bench_dist2_gloo 600 python bench.py --gpus 2 --dist-backend gloo --steps 10 \
+    dist2) run bench_dist2_gloo 600 python bench.py --full --gpus 2 --dist-backend gloo --steps 10 \
                --warmup 3 --no-cpu ;;
     rgprof) GINE_HIP_LIB=raincast-gnn_amd/raincast_gnn/_native/var/rgprof/libgine_hip.so run rg_prof 300 python tools/rg_prof.py ;;
     var)   for v in raincast-gnn_amd/csrc/build/var/*/; do n=$(basename "$v")
-             GINE_HIP_LIB=${v}libgine_hip.so run var_${n}_base 300 python bench.py --no-cpu --steps 30 ${VARARGS:-}
+             GINE_HIP_LIB=${v}libgine_hip.so run var_${n}_base 300 python bench.py --full --no-cpu --steps 30 ${VARARGS:-}
            done ;;
-    varbase) run var_base 300 python bench.py --no-cpu --steps 30 ${VARARGS:-} ;;
+    varbase) run var_base 300 python bench.py --full --no-cpu --steps 30 ${VARARGS:-} ;;
     mpmicro) run mp_micro 300 python tools/mp_micro.py ${MPARGS:-} ;;
     mpvar) for v in raincast-gnn_amd/csrc/build/var/*/; do n=$(basename "$v")
              GINE_HIP_LIB=${v}libgine_hip.so run mp_micro_${n} 300 python tools/mp_micro.py ${MPARGS:-}
@@ -111,7 +111,7 @@ PY
            run ds_sq2 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_VMEM_RD --output-format csv -d "$OUT/ds_sq2" -o run -- \
                python3 tools/ds_micro.py --reps 5 --nodes 16000 ;;
     sq)    run pmc_sq 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA --output-format csv -d "$OUT/pmc_sq" -o run -- \
-               python3 bench.py --steps 5 --warmup 2 --no-cpu --no-graph --kernel-reps 5 ;;
+               python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-graph --kernel-reps 5 ;;
   esac
 done
 echo "session done" | tee -a "$OUT/session.log"
