@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GINE_ABI_VERSION 8  /* 2: adamw step-state query, gine_count_valid, window plan slot/edge_begin;
+#define GINE_ABI_VERSION 9  /* 2: adamw step-state query, gine_count_valid, window plan slot/edge_begin;
                               3: gine_deepset_bwd_num_partials takes the hidden width;
                               4: bn_acc grows two grid-barrier words (gine_mp_fwd_layer);
                               5: grid-barrier failure count (gine_bn_acc_barrier_failures_index),
@@ -38,7 +38,10 @@ extern "C" {
                               6: gine_mlp_bwd_layer again, in the forward layer's role-split form;
                               7: gine_mp_fwd_layer takes the layer window plan
                                  (gine_graph_plan_layer_windows, gine_mp_fwd_layer_windows_fit);
-                              8: gine_mp_fwd_layer can also run the output head (gine_layer_head) */
+                              8: gine_mp_fwd_layer can also run the output head (gine_layer_head);
+                              9: the seven entry points of the singly folded dense chain are removed
+                                 (the doubly folded form is the chain; the unfolded one stays as
+                                 the tests' comparator) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -590,17 +593,13 @@ int gine_deepset_mask_layout(int64_t num_nodes, int32_t hidden, int32_t* nodes_p
 int gine_deepset_fwd(const float* ens, const float* w1, const float* b1, float* r,
                      uint16_t* mask, int64_t num_nodes, int32_t members, int32_t in_features,
                      int32_t hidden, void* stream);
-/* gine_deepset_fwd plus the dense chain's folded dim_red weight (W' | b' | W'^T of
- * gine_chain_fwd_folded, hidden in {64, 128}, x_features <= 64) into wfold, computed by
- * extra workgroups of the same launch for gine_chain_fwd_folded3. */
-int gine_deepset_fwd_fold(const float* ens, const float* w1, const float* b1, float* r,
-                          uint16_t* mask, int64_t num_nodes, int32_t members,
-                          int32_t in_features, int32_t hidden, const float* wr1,
-                          const float* br1, const float* wdr, const float* bdr, float* wfold,
-                          int32_t x_features, void* stream);
-/* gine_deepset_fwd_fold plus the doubly folded chain's [Wf | bf] (Wf = Wr0 Wp2 [D][D],
- * bf = members * Wr0 bp2 + br0 [D]) into wfold2 [D*D + D], by a second set of extra
- * workgroups, for gine_chain_fwd_folded2 (wr0 / br0 = rho[0], wp2 / bp2 = phi[2]). */
+/* gine_deepset_fwd plus the dense chain's two folded weights, computed from the current
+ * weights by extra workgroups of the same launch, for gine_chain_fwd_folded2 (hidden = D in
+ * {64, 128}, x_features = F <= 64; wr1 / br1 = rho[2], wdr / bdr = dim_red, wr0 / br0 =
+ * rho[0], wp2 / bp2 = phi[2]; every pointer required):
+ *   wfold  [2*D*(F+D) + D] = W' [D][F+D] | b' [D] | W'^T [F+D][D],
+ *          W' = [Wdr_x | Wdr_e Wr1], b' = Wdr_e br1 + bdr;
+ *   wfold2 [D*D + D] = Wf [D][D] | bf [D],  Wf = Wr0 Wp2, bf = members * Wr0 bp2 + br0. */
 int gine_deepset_fwd_fold2(const float* ens, const float* w1, const float* b1, float* r,
                            uint16_t* mask, int64_t num_nodes, int32_t members,
                            int32_t in_features, int32_t hidden, const float* wr1,
@@ -643,91 +642,28 @@ int gine_head_bwd_reduce(const float* slab, float* dw, float* db, int64_t num_no
 /* ------------------------------------------------------------------------------------
  * Dense layers between the DeepSet member sum and the GINE stack (models/gnn.py:48-68,
  * 112-113, 132-135), phi's last Linear applied after the member sum:
- *   s = r Wp2^T + bias_scale * bp2;  u = relu(s Wr0^T + br0);  e = u Wr1^T + br1;
+ *   s = r Wp2^T + M bp2;  u = relu(s Wr0^T + br0);  e = u Wr1^T + br1;
  *   h0 = [x | e] Wdr^T + bdr
- * r [N, D] = gine_deepset_fwd output, x [N, F] node features, D in {64, 128}, F <= 64.
- * gine_chain_fwd writes s, u, e (saved for the backward) and h0.
- * gine_chain_bwd, from dh0 = d loss / d h0: de = dh0 Wdr[:, F:], dt = (de Wr1) * 1[u > 0],
- *   ds = dt Wr0, dr = ds Wp2 (dr feeds gine_deepset_bwd), and all eight parameter
- *   gradients (dbp2 scaled by bias_scale; bias pointers may be NULL) through
- *   gine_chain_bwd_slab_floats() floats of partials reduced in fixed order.
+ * r [N, D] = the DeepSet forward's output, x [N, F] node features, M = members, D in
+ * {64, 128}, F <= 64.  The chain runs doubly folded: only the ReLU separates its Linears, so
+ *   u = relu(r Wf^T + bf), Wf = Wr0 Wp2, bf = M Wr0 bp2 + br0     (wfold2)
+ *   h0 = [x | u] W'^T + b', W' = [Wdr_x | Wdr_e Wr1], b' = Wdr_e br1 + bdr   (wfold)
+ * with wfold / wfold2 from gine_deepset_fwd_fold2; s, e and their gradients are never formed.
+ * gine_chain_fwd_folded2: u (saved for the backward) and h0, one launch.
+ * gine_chain_bwd_folded2, from dh0 = d loss / d h0: dt = (dh0 Wc) * 1[u > 0] (Wc = W'[:, F:]),
+ *   dr = dt Wf (dr feeds gine_deepset_bwd), one launch.
+ * gine_chain_wgrad_folded2: one engine launch for G = dh0^T [x | u] | g = sum_n dh0 (gfold
+ *   [D*(F+D) + D]) and G2 = dt^T r | g2 = sum_n dt (g2fold [D*D + D]) through a slab of
+ *   gine_chain_bwd_slab_floats() floats of partials reduced in fixed order; gfold = g2fold =
+ *   NULL leaves the slab for gine_grad_finalize_batch (job:
+ *   gine_chain_wgrad_folded2_grad_job).
+ * gine_chain_unfold_grads2, after the reduction, one launch (fp32 MFMA; bias outputs may be
+ *   NULL): dWdr = [G_x | G_u Wr1^T + g br1^T], dbdr = g, dWr1 = Wdr_e^T G_u,
+ *   dbr1 = Wdr_e^T g, dWr0 = G2 Wp2^T + M g2 bp2^T, dbr0 = g2, dWp2 = Wr0^T G2,
+ *   dbp2 = M Wr0^T g2.
  * ---------------------------------------------------------------------------------- */
-int gine_chain_fwd(const float* r, const float* x, const float* wp2, const float* bp2,
-                   float bias_scale, const float* wr0, const float* br0, const float* wr1,
-                   const float* br1, const float* wdr, const float* bdr, float* s, float* u,
-                   float* e, float* h0, int64_t num_nodes, int32_t hidden,
-                   int32_t in_features, void* stream);
 int gine_chain_bwd_slab_floats(int64_t num_nodes, int32_t hidden, int32_t in_features,
                                size_t* floats);
-int gine_chain_bwd(const float* dh0, const float* x, const float* r, const float* s,
-                   const float* u, const float* e, const float* wp2, const float* wr0,
-                   const float* wr1, const float* wdr, float* de, float* dt, float* ds,
-                   float* dr, float* slab, float* dwp2, float* dbp2, float bias_scale,
-                   float* dwr0, float* dbr0, float* dwr1, float* dbr1, float* dwdr,
-                   float* dbdr, int64_t num_nodes, int32_t hidden, int32_t in_features,
-                   void* stream);
-/* The parameter-gradient half of gine_chain_bwd on its own (call gine_chain_bwd with
- * slab = NULL for the input-gradient half): lets it run on another stream, beside the
- * DeepSet backward that consumes dr. */
-int gine_chain_wgrad(const float* dh0, const float* x, const float* r, const float* s,
-                     const float* u, const float* e, const float* de, const float* dt,
-                     const float* ds, float* slab, float* dwp2, float* dbp2, float bias_scale,
-                     float* dwr0, float* dbr0, float* dwr1, float* dbr1, float* dwdr,
-                     float* dbdr, int64_t num_nodes, int32_t hidden, int32_t in_features,
-                     void* stream);
-
-/* Folded chain (the default path of raincast_gnn.chain): rho[2] and dim_red have no
- * nonlinearity between them, so h0 = [x | u] W'^T + b' with W' = [Wdr_x | Wdr_e Wr1],
- * b' = Wdr_e br1 + bdr, and e / de are never formed.
- * gine_chain_fwd_folded writes s, u, h0 and W' [D][F+D] | b' [D] | W'^T [F+D][D] into
- *   wfold [2*D*(F+D) + D] (saved for the backward; folded from the current weights by every
- *   call).
- * gine_chain_bwd_folded: dt = (dh0 Wc) * 1[u > 0] (Wc = W'[:, F:]), ds = dt Wr0, dr = ds Wp2.
- * gine_chain_wgrad_folded: one engine launch for G = dh0^T [x | u] | g = sum_n dh0 (into
- *   gfold [D*(F+D) + D]), dWr0 | dbr0 and dWp2 | dbp2 (dbp2 scaled by bias_scale); slab of
- *   gine_chain_bwd_slab_floats() floats.  gfold = dwr0 = dwp2 = NULL leaves the slab for
- *   gine_grad_finalize_batch (job from gine_chain_wgrad_folded_grad_job).
- * gine_chain_unfold_grads, after the reduction: dWdr = [G_x | G_u Wr1^T + g br1^T],
- *   dbdr = g, dWr1 = Wdr_e^T G_u, dbr1 = Wdr_e^T g (fp32 MFMA; bias outputs may be NULL).
- * Replaces the same reference modules as gine_chain_fwd / gine_chain_bwd. */
-int gine_chain_fwd_folded(const float* r, const float* x, const float* wp2, const float* bp2,
-                          float bias_scale, const float* wr0, const float* br0,
-                          const float* wr1, const float* br1, const float* wdr,
-                          const float* bdr, float* wfold, float* s, float* u, float* h0,
-                          int64_t num_nodes, int32_t hidden, int32_t in_features, void* stream);
-/* The folded forward in ONE launch (s -> u -> h0), W' | b' | W'^T already in wfold (folded
- * by gine_deepset_fwd_fold in the launch before). */
-int gine_chain_fwd_folded3(const float* r, const float* x, const float* wp2, const float* bp2,
-                           float bias_scale, const float* wr0, const float* br0,
-                           const float* wfold, float* s, float* u, float* h0, int64_t num_nodes,
-                           int32_t hidden, int32_t in_features, void* stream);
-int gine_chain_bwd_folded(const float* dh0, const float* u, const float* wp2, const float* wr0,
-                          const float* wfold, float* dt, float* ds, float* dr,
-                          int64_t num_nodes, int32_t hidden, int32_t in_features, void* stream);
-int gine_chain_wgrad_folded(const float* dh0, const float* x, const float* r, const float* s,
-                            const float* u, const float* dt, const float* ds, float* slab,
-                            float* gfold, float* dwr0, float* dbr0, float* dwp2, float* dbp2,
-                            float bias_scale, int64_t num_nodes, int32_t hidden,
-                            int32_t in_features, void* stream);
-int gine_chain_wgrad_folded_grad_job(int64_t num_nodes, int32_t hidden, int32_t in_features,
-                                     const float* slab, float bias_scale, float* gfold,
-                                     float* dwr0, float* dbr0, float* dwp2, float* dbp2,
-                                     gine_grad_job* job);
-int gine_chain_unfold_grads(const float* gfold, const float* wr1, const float* br1,
-                            const float* wdr, float* dwdr, float* dbdr, float* dwr1,
-                            float* dbr1, int32_t hidden, int32_t in_features, void* stream);
-
-/* Doubly folded chain (raincast_gnn.chain.FOLD2): phi[2] is followed by rho[0] with only the
- * member sum between them, so pre = s Wr0^T + br0 = r Wf^T + bf with Wf = Wr0 Wp2,
- * bf = M Wr0 bp2 + br0 (wfold2, from gine_deepset_fwd_fold2); s / ds are never formed.
- * gine_chain_fwd_folded2: u = relu(r Wf^T + bf), h0 = [x | u] W'^T + b' (one launch).
- * gine_chain_bwd_folded2: dt = (dh0 Wc) * 1[u > 0], dr = dt Wf (one launch).
- * gine_chain_wgrad_folded2: one engine launch for G = dh0^T [x | u] | g (gfold
- *   [D*(F+D) + D]) and G2 = dt^T r | g2 = sum_n dt (g2fold [D*D + D]); gfold = g2fold = NULL
- *   leaves the slab for gine_grad_finalize_batch (job: gine_chain_wgrad_folded2_grad_job).
- * gine_chain_unfold_grads2, after the reduction, one launch: gine_chain_unfold_grads's
- *   outputs plus dWr0 = G2 Wp2^T + M g2 bp2^T, dbr0 = g2, dWp2 = Wr0^T G2,
- *   dbp2 = M Wr0^T g2 (M = members; bias outputs may be NULL). */
 int gine_chain_fwd_folded2(const float* r, const float* x, const float* wfold,
                            const float* wfold2, float* u, float* h0, int64_t num_nodes,
                            int32_t hidden, int32_t in_features, void* stream);
@@ -747,6 +683,34 @@ int gine_chain_unfold_grads2(const float* gfold, const float* wr1, const float* 
                              const float* bp2, const float* wr0, float* dwr0, float* dbr0,
                              float* dwp2, float* dbp2, float members, int32_t hidden,
                              int32_t in_features, void* stream);
+/* The same chain unfolded, kept as the comparator the tests hold the folded form against
+ * (raincast_gnn.chain.FOLD = False; slower): two launches each way.
+ * gine_chain_fwd writes s, u, e (saved for the backward) and h0 (bias_scale = M).
+ * gine_chain_bwd, from dh0: de = dh0 Wdr[:, F:], dt = (de Wr1) * 1[u > 0], ds = dt Wr0,
+ *   dr = ds Wp2, and with slab != NULL all eight parameter gradients (dbp2 scaled by
+ *   bias_scale; bias pointers may be NULL) through gine_chain_bwd_slab_floats() floats.
+ * gine_chain_wgrad: the parameter-gradient half on its own (gine_chain_bwd with slab = NULL
+ *   is the input-gradient half); all four weight outputs NULL leaves the slab for
+ *   gine_grad_finalize_batch (job: gine_chain_wgrad_grad_job). */
+int gine_chain_fwd(const float* r, const float* x, const float* wp2, const float* bp2,
+                   float bias_scale, const float* wr0, const float* br0, const float* wr1,
+                   const float* br1, const float* wdr, const float* bdr, float* s, float* u,
+                   float* e, float* h0, int64_t num_nodes, int32_t hidden,
+                   int32_t in_features, void* stream);
+int gine_chain_bwd(const float* dh0, const float* x, const float* r, const float* s,
+                   const float* u, const float* e, const float* wp2, const float* wr0,
+                   const float* wr1, const float* wdr, float* de, float* dt, float* ds,
+                   float* dr, float* slab, float* dwp2, float* dbp2, float bias_scale,
+                   float* dwr0, float* dbr0, float* dwr1, float* dbr1, float* dwdr,
+                   float* dbdr, int64_t num_nodes, int32_t hidden, int32_t in_features,
+                   void* stream);
+int gine_chain_wgrad(const float* dh0, const float* x, const float* r, const float* s,
+                     const float* u, const float* e, const float* de, const float* dt,
+                     const float* ds, float* slab, float* dwp2, float* dbp2, float bias_scale,
+                     float* dwr0, float* dbr0, float* dwr1, float* dbr1, float* dwdr,
+                     float* dbdr, int64_t num_nodes, int32_t hidden, int32_t in_features,
+                     void* stream);
+
 
 /* Measurement utility (not on the hot path): copy `bytes` (a multiple of 16) from src to dst
  * with 16-byte-per-lane streaming loads and stores -- the HBM copy ceiling bench.py prices

@@ -1,7 +1,7 @@
-// Folding rho[2] into dim_red for the folded dense chain (gine_chain.hip): the W' / b' /
-// W'^T tiles, built by extra workgroups of whichever launch precedes the chain's use of
-// them (the first chain kernel, or the DeepSet forward -- gine_deepset_fwd_fold), and the
-// small K-split MFMA tile helpers the unfold kernel shares.
+// The dense chain's two folds (gine_chain.hip): rho[2] into dim_red (W' / b' / W'^T) and
+// phi[2] into rho[0] (Wf / bf), built tile by tile from the current weights by extra
+// workgroups of the DeepSet forward (gine_deepset_fwd_fold2), which precedes the chain's use
+// of them; and the small K-split MFMA tile helpers the gradient unfold kernel shares.
 #pragma once
 
 #include "gine_common.hpp"
@@ -77,10 +77,12 @@ __device__ __forceinline__ float ksplit_sum(const float* sR, int row, int col) {
   return v;
 }
 
+// rho[2] is followed by dim_red with no nonlinearity between them, so
+//   h0 = [x | u Wr1^T + br1] Wdr^T + bdr = [x | u] W'^T + b'.
 // One [32 x 32] tile (rows k0, columns c0 of Wc) of W' = [Wdr_x | Wc], Wc = Wdr_e Wr1, and
-// (c0 = 0) the x columns and b' = Wdr_e br1 + bdr of its rows: the folded chain's dim_red
-// weight, written as W' [D][F+D], b' [D] and W'^T [F+D][D] (the forward kernel's B
-// fragments read W'^T along rows, coalesced).  Run by the fold workgroups of F1.
+// (c0 = 0) the x columns and b' = Wdr_e br1 + bdr of its rows, written as W' [D][F+D],
+// b' [D] and W'^T [F+D][D] (the forward kernel's B fragments read W'^T along rows,
+// coalesced).  Run by the first kFoldBlocks<D> workgroups of gine_deepset_fwd_fold2.
 template <int D>
 __device__ void fold_tile(const FoldArgs& a, int ft, float* sA, float* sR, int c32, int h) {
   constexpr int NT = 2 * D, LDA = D + 4, T = D / 32;
@@ -107,7 +109,7 @@ __device__ void fold_tile(const FoldArgs& a, int ft, float* sA, float* sR, int c
     }
   }
   const float bv = threadIdx.x < D ? a.fb_r1[threadIdx.x] : 0.f;
-  __syncthreads();  // every wave is done with sA / sB
+  __syncthreads();
 #pragma unroll
   for (int i = 0; i < SI; ++i) {
     const int idx = threadIdx.x + i * NT;
@@ -146,16 +148,16 @@ __device__ void fold_tile(const FoldArgs& a, int ft, float* sA, float* sR, int c
   }
 }
 
-// The double fold (gine_chain_fwd_folded2): phi[2] is followed by rho[0] with no
-// nonlinearity between them either (the member sum sits in between, and a Linear commutes
-// with it), so  rho[0](s) = r Wf^T + bf  with  Wf = Wr0 Wp2,  bf = M Wr0 bp2 + br0.
+// phi[2] is followed by rho[0] with no nonlinearity between them either (the member sum
+// sits in between, and a Linear commutes with it), so  rho[0](s) = r Wf^T + bf  with
+// Wf = Wr0 Wp2,  bf = M Wr0 bp2 + br0.
 // One [32 x 32] tile (rows k0, columns c0) of Wf into wfold2 ([D][D], then bf [D] by the
 // tiles of column 0): A = Wr0's rows staged in sA, B = Wp2's columns.  Run by the second
-// set of fold workgroups of gine_deepset_fwd_fold2.
+// kFoldBlocks<D> workgroups of gine_deepset_fwd_fold2.
 struct Fold2Args {
   const float *w_r0, *b_r0, *w_p2, *b_p2;
   float members;
-  float* wfold2;  // NULL: no double fold
+  float* wfold2;
 };
 
 template <int D>
@@ -200,11 +202,8 @@ __device__ void fold2_tile(const Fold2Args& a, int ft, float* sA, float* sR, int
   }
 }
 
-// F1 of the folded chain launches (D/32)^2 workgroups more than its chain grid: block
-// chain_blocks + t folds tile t of W' beside the chain tiles (they fit on the CUs next to
-// the one chain workgroup per CU).
+// workgroups of one fold: a [32 x 32] tile of its D x D product each
 template <int D>
 constexpr int kFoldBlocks = (D / 32) * (D / 32);
-
 
 }  // namespace gine

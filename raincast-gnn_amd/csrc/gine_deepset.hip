@@ -447,8 +447,8 @@ __device__ __forceinline__ void walk_tiles(const Groups& gr, int GM, int tpg,
 // memory operations in flight and the next tiles' loads stay in flight under the MFMAs
 // (a conditional store there made it drain the whole queue -- s_waitcnt vmcnt(0) -- every
 // tile).
-// FOLD (gine_deepset_fwd_fold): the first kFoldBlocks<H> workgroups fold the dense chain's
-// dim_red weight (gine_chainfold.hpp) beside the member sums, for the chain's one-launch
+// FOLD (gine_deepset_fwd_fold2): the first 2 kFoldBlocks<H> workgroups fold the dense
+// chain's weights (W' then Wf, gine_chainfold.hpp) beside the member sums, for the chain's
 // forward that follows.  They are dealt first (so they never wait for a free slot behind the
 // walk) and share one LDS buffer with the walk's tiles (so the walk's occupancy is that of
 // the larger of the two, not of their sum).
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(2 * H, 4) void k_deepset_fwd(const float* __restric
   __shared__ __attribute__((aligned(16))) float s_lds[kWalk > kFold ? kWalk : kFold];
   int nbw = gridDim.x, bw = blockIdx.x;  // workgroups walking the groups, this one's index
   if constexpr (FOLD) {
-    const int nfold = kFoldBlocks<H> * (fold2.wfold2 != nullptr ? 2 : 1);
+    constexpr int nfold = 2 * kFoldBlocks<H>;
     nbw -= nfold;
     bw -= nfold;
     if (bw < 0) {
@@ -983,24 +983,27 @@ extern "C" int gine_debug_ds_prof(long long* out, int* n) {
 }
 #endif
 
-namespace {
-int deepset_fwd_fold(const float* ens, const float* w1, const float* b1, float* r,
-                     uint16_t* mask, int64_t num_nodes, int32_t members, int32_t in_features,
-                     int32_t hidden, const FoldArgs& fold, const Fold2Args& fold2,
-                     void* stream) {
+extern "C" int gine_deepset_fwd_fold2(const float* ens, const float* w1, const float* b1,
+                                      float* r, uint16_t* mask, int64_t num_nodes,
+                                      int32_t members, int32_t in_features, int32_t hidden,
+                                      const float* wr1, const float* br1, const float* wdr,
+                                      const float* bdr, float* wfold, int32_t x_features,
+                                      const float* wr0, const float* br0, const float* wp2,
+                                      const float* bp2, float* wfold2, void* stream) {
+  if (!wr0 || !br0 || !wp2 || !bp2 || !wfold2) return GINE_ERR_INVALID;
   const int KP = pad_fwd(in_features);
   if ((hidden != 64 && hidden != 128) || KP < 0 || in_features <= 0) return GINE_ERR_DIM;
-  if (fold.F < 1 || fold.F > 64) return GINE_ERR_DIM;
+  if (x_features < 1 || x_features > 64) return GINE_ERR_DIM;
   if (num_nodes < 0 || members <= 0) return GINE_ERR_INVALID;
-  if (!fold.fw_r1 || !fold.fb_r1 || !fold.fw_dr || !fold.fb_dr || !fold.wfold)
-    return GINE_ERR_INVALID;
+  if (!wr1 || !br1 || !wdr || !bdr || !wfold) return GINE_ERR_INVALID;
+  const FoldArgs fold{wr1, br1, wdr, bdr, wfold, x_features};
+  const Fold2Args fold2{wr0, br0, wp2, bp2, (float)members, wfold2};
   if (num_nodes > 0 && (!ens || !w1 || !b1 || !r)) return GINE_ERR_INVALID;
   if (num_nodes * members >= (int64_t(1) << 31)) return GINE_ERR_TOO_LARGE;
   const int groups = num_groups(num_nodes, hidden);
   const int walk = num_nodes > 0 ? std::min(groups, 1024) : 0;
   const int G = nodes_per_half(num_nodes, hidden);
-  const int nfold = (hidden == 64 ? kFoldBlocks<64> : kFoldBlocks<128>) *
-                    (fold2.wfold2 != nullptr ? 2 : 1);
+  const int nfold = 2 * (hidden == 64 ? kFoldBlocks<64> : kFoldBlocks<128>);
   hipStream_t s = as_stream(stream);
 #define LAUNCH_FWD_F(H_, KP_, G_, MK_)                                                        \
   hipLaunchKernelGGL((k_deepset_fwd<H_, KP_, G_, MK_, true>), dim3(walk + nfold),             \
@@ -1027,29 +1030,4 @@ int deepset_fwd_fold(const float* ens, const float* w1, const float* b1, float* 
 #undef LAUNCH_FWD_F
   GINE_LAUNCH_STATUS();
   return GINE_OK;
-}
-}  // namespace
-
-extern "C" int gine_deepset_fwd_fold(const float* ens, const float* w1, const float* b1,
-                                     float* r, uint16_t* mask, int64_t num_nodes,
-                                     int32_t members, int32_t in_features, int32_t hidden,
-                                     const float* wr1, const float* br1, const float* wdr,
-                                     const float* bdr, float* wfold, int32_t x_features,
-                                     void* stream) {
-  return deepset_fwd_fold(ens, w1, b1, r, mask, num_nodes, members, in_features, hidden,
-                          FoldArgs{wr1, br1, wdr, bdr, wfold, x_features}, Fold2Args{},
-                          stream);
-}
-
-extern "C" int gine_deepset_fwd_fold2(const float* ens, const float* w1, const float* b1,
-                                      float* r, uint16_t* mask, int64_t num_nodes,
-                                      int32_t members, int32_t in_features, int32_t hidden,
-                                      const float* wr1, const float* br1, const float* wdr,
-                                      const float* bdr, float* wfold, int32_t x_features,
-                                      const float* wr0, const float* br0, const float* wp2,
-                                      const float* bp2, float* wfold2, void* stream) {
-  if (!wr0 || !br0 || !wp2 || !bp2 || !wfold2) return GINE_ERR_INVALID;
-  return deepset_fwd_fold(ens, w1, b1, r, mask, num_nodes, members, in_features, hidden,
-                          FoldArgs{wr1, br1, wdr, bdr, wfold, x_features},
-                          Fold2Args{wr0, br0, wp2, bp2, (float)members, wfold2}, stream);
 }

@@ -23,7 +23,7 @@ GINE_MP_BWD_SELF = 1
 GINE_MP_LIN_MULADD = 2
 EPI_NONE, EPI_RELU, EPI_RESIDUAL_RELU = 0, 1, 2
 LOSS_NORMAL, LOSS_MIXED_NORMAL, LOSS_MIXED, LOSS_MIXED_U = 0, 1, 2, 3
-ABI_VERSION = 8
+ABI_VERSION = 9
 COUNT_PARTS = 64  # GINE_COUNT_PARTS
 
 _c_void_p = ctypes.c_void_p
@@ -90,8 +90,6 @@ _SIGNATURES = {
                                  _c_void_p],
     "gine_grad_finalize_batch": [_job_p, _i32, _c_void_p],
     "gine_head_bwd_grad_job": [_i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _job_p],
-    "gine_chain_wgrad_grad_job": [_i64, _i32, _i32, _c_void_p, _f32] + [_c_void_p] * 8
-                                 + [_job_p],
     "gine_deepset_bwd_grad_job": [_i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _job_p],
     "gine_mlp_num_partials": [_i64, _i32, ctypes.POINTER(_i32)],
     "gine_mlp_fwd1": [_c_void_p] * 5 + [_i64, _i32, _c_void_p],
@@ -125,8 +123,6 @@ _SIGNATURES = {
     "gine_mlp_wgrad_num_chunks": [_i64, _i32, ctypes.POINTER(_i32)],
     "gine_mlp_wgrad": [_c_void_p] * 13 + [_i64, _i32, _i32, _c_void_p],
     "gine_mlp_bwd1_wgrad": [_c_void_p] * 15 + [_i64, _i32, _i32, _c_void_p],
-    "gine_chain_wgrad": [_c_void_p] * 12 + [_f32] + [_c_void_p] * 6 + [_i64, _i32, _i32,
-                                                                        _c_void_p],
     "gine_head_bwd_reduce": [_c_void_p] * 3 + [_i64, _i32, _i32, _c_void_p],
     "gine_adamw_step": [_c_void_p] * 5 + [_i64, _f32, _f32, _f32, _f32, _f32, _c_void_p],
     "gine_crps_num_partials": [_i64, ctypes.POINTER(_i32)],
@@ -157,23 +153,16 @@ _SIGNATURES = {
     "gine_head_fwd_count": [_c_void_p] * 5 + [_i64, _i32, _i32] + [_c_void_p] * 3,
     "gine_head_bwd_slab_floats": [_i64, _i32, _i32, ctypes.POINTER(_size)],
     "gine_head_bwd": [_c_void_p] * 8 + [_i64, _i32, _i32, _c_void_p],
+    "gine_chain_bwd_slab_floats": [_i64, _i32, _i32, ctypes.POINTER(_size)],
     "gine_chain_fwd": [_c_void_p] * 4 + [_f32] + [_c_void_p] * 10 + [_i64, _i32, _i32,
                                                                        _c_void_p],
-    "gine_chain_bwd_slab_floats": [_i64, _i32, _i32, ctypes.POINTER(_size)],
     "gine_chain_bwd": [_c_void_p] * 17 + [_f32] + [_c_void_p] * 6 + [_i64, _i32, _i32,
                                                                        _c_void_p],
+    "gine_chain_wgrad": [_c_void_p] * 12 + [_f32] + [_c_void_p] * 6 + [_i64, _i32, _i32,
+                                                                        _c_void_p],
+    "gine_chain_wgrad_grad_job": [_i64, _i32, _i32, _c_void_p, _f32] + [_c_void_p] * 8
+                                 + [_job_p],
     "gine_graph_plan_window_slots": [_c_void_p, _c_void_p, _i32, _c_void_p],
-    "gine_chain_fwd_folded": [_c_void_p] * 4 + [_f32] + [_c_void_p] * 10 + [_i64, _i32, _i32,
-                                                                              _c_void_p],
-    "gine_chain_bwd_folded": [_c_void_p] * 8 + [_i64, _i32, _i32, _c_void_p],
-    "gine_chain_fwd_folded3": [_c_void_p] * 4 + [_f32] + [_c_void_p] * 6 + [_i64, _i32, _i32,
-                                                                             _c_void_p],
-    "gine_deepset_fwd_fold": [_c_void_p] * 5 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 5
-                             + [_i32, _c_void_p],
-    "gine_chain_wgrad_folded": [_c_void_p] * 13 + [_f32, _i64, _i32, _i32, _c_void_p],
-    "gine_chain_wgrad_folded_grad_job": [_i64, _i32, _i32, _c_void_p, _f32] + [_c_void_p] * 5
-                                        + [_job_p],
-    "gine_chain_unfold_grads": [_c_void_p] * 8 + [_i32, _i32, _c_void_p],
     "gine_deepset_fwd_fold2": [_c_void_p] * 5 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 5
                               + [_i32] + [_c_void_p] * 6,
     "gine_chain_fwd_folded2": [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p],

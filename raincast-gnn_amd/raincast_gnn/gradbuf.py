@@ -99,7 +99,7 @@ def deferrable(*outs) -> bool:
 def defer(job: "_lib.GradJob", device: torch.device, keep_alive=(), post=None) -> None:
     """Queue ``job`` (its buffers kept alive) for the end-of-backward batch launch.
     ``post(stream)``, if given, is called after the batch launches of that stream (work that
-    reads the job's reduced outputs, e.g. gine_chain_unfold_grads)."""
+    reads the job's reduced outputs, e.g. gine_chain_unfold_grads2)."""
     stream = _lib.stream_handle(device)
     with _pending_lock:
         first = not _pending

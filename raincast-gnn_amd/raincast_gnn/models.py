@@ -127,17 +127,15 @@ class GNN(nn.Module):
         lins = (lin2, rho0, rho1, self.dim_red)
         if (isinstance(act, nn.ReLU) and isinstance(rho_act, nn.ReLU)
                 and deepset.fusable(ens, lin1.weight, lin1.bias)):
-            if (fused_chain.FOLD and fused_chain.F3
-                    and (fused_chain.FOLD2 or ens.size(0) <= fused_chain.F3_MAX_NODES)
-                    and fused_chain.fusable_dims(lin1.out_features, x, lins)):
-                # the DeepSet launch also folds dim_red; the chain forward is one launch
-                fold = ((rho1, self.dim_red, rho0, lin2) if fused_chain.FOLD2
-                        else (rho1, self.dim_red))
-                r, wfold = deepset.phi_sum(ens, lin1, fold=fold)
-                return fused_chain.chain(r, x, lins, ens.size(1), wfold=wfold)
+            if fused_chain.fusable_dims(lin1.out_features, x, lins):
+                if not fused_chain.FOLD:  # the unfolded comparator
+                    r = deepset.phi_sum(ens, lin1)
+                    assert fused_chain.fusable(r, x, lins)
+                    return fused_chain.chain(r, x, lins, ens.size(1))
+                # the DeepSet launch also folds the chain's weights; the chain is one launch
+                r, wfold = deepset.phi_sum(ens, lin1, fold=(rho1, self.dim_red, rho0, lin2))
+                return fused_chain.chain(r, x, lins, ens.size(1), wfold)
             r = deepset.phi_sum(ens, lin1)
-            if fused_chain.fusable(r, x, lins):
-                return fused_chain.chain(r, x, lins, ens.size(1))
             emb = ds.rho(lin2(r, bias_scale=ens.size(1)))
             return self.dim_red(torch.cat([x, emb], dim=1))
         emb = ds(ens)

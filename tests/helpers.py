@@ -256,17 +256,15 @@ class EngineTies:
         h0 = self._front
         assert h0 is not None and h0.grad_fn is not None, "the fused chain did not run"
         sv = h0.grad_fn.saved_tensors
-        if type(h0.grad_fn).__name__.startswith("_ChainFolded2Fn"):
-            # doubly folded chain (r, x, u, wfold, ...): rho[0]'s pre-activation is
-            # r Wf^T + bf with the engine's folded [Wf | bf] at the tail of wfold
-            r_e, u, wfold = sv[0], sv[2], sv[3]
-            H = u.size(1)
-            tail = wfold.detach().cpu().double()[-(H * H + H):]
-            self.s, self.r_e = None, ref(r_e).double()
-            self.wf, self.bf = tail[:H * H].view(H, H), tail[H * H:]
-            self.u = ref(u)
-        else:
-            self.s, self.u, self.r_e = ref(sv[2]).double(), ref(sv[3]), None
+        assert type(h0.grad_fn).__name__.startswith("_ChainFolded2Fn"), type(h0.grad_fn)
+        # doubly folded chain (r, x, u, wfold, ...): rho[0]'s pre-activation is
+        # r Wf^T + bf with the engine's folded [Wf | bf] at the tail of wfold
+        r_e, u, wfold = sv[0], sv[2], sv[3]
+        H = u.size(1)
+        tail = wfold.detach().cpu().double()[-(H * H + H):]
+        self.s, self.r_e = None, ref(r_e).double()
+        self.wf, self.bf = tail[:H * H].view(H, H), tail[H * H:]
+        self.u = ref(u)
         ds_fn = h0.grad_fn.next_functions[0][0]
         ens, mask = ds_fn.saved_tensors[:2]
         N, M, _ = ens.shape

@@ -82,6 +82,11 @@ def test_grad_batch_validation_without_device():
     assert lib.gine_chain_wgrad_grad_job(16000, 128, 35, p, 11.0, *([p] * 8),
                                          ctypes.byref(job)) == 0
     assert job.nz == 4 and job.wsize[0] == 128 * 163 and job.bscale[3] == 11.0
+    assert lib.gine_chain_wgrad_folded2_grad_job(16000, 128, 35, p, p, p,
+                                                 ctypes.byref(job)) == 0
+    assert job.nz == 2 and job.wsize[0] == 128 * 163 and job.wsize[1] == 128 * 128
+    assert all(job.per[z] == job.wsize[z] + 128 for z in range(2))
+    assert job.bscale[0] == 1.0 and job.bscale[1] == 1.0
     assert lib.gine_deepset_bwd_grad_job(16000, 35, 128, p, p, p, ctypes.byref(job)) == 0
     assert job.wsize[0] == 128 * 35 and job.per[0] == 128 * 36
 

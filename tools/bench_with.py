@@ -2,7 +2,7 @@
 """bench.py with engine path selections overridden (raincast_gnn.options; the product path
 reads no environment switches), for A/B runs on one box:
     python tools/bench_with.py ENGINE_IN_MP=0 MP_FUSED=0 -- --config 5 --steps 20 --no-cpu
-    python tools/bench_with.py chain.FOLD2=0 -- --steps 50 --no-cpu   (module.NAME: that
+    python tools/bench_with.py chain.FOLD=0 -- --steps 50 --no-cpu   (module.NAME: that
     raincast_gnn module's switch)
 Values: 0/1 for booleans, strings otherwise."""
 import importlib

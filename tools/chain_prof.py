@@ -1,4 +1,4 @@
-"""Phase profile of the doubly folded chain kernels (k_chain F2D forward / B2D backward) at
+"""Phase profile of the dense chain's two row kernels (k_chain forward / backward) at
 cfg2's shape: every workgroup's s_memtime stamps (gine_chain.hip GINE_CHAIN_PROFILE).
     GINE_HIP_LIB=.../var/chainprof/libgine_hip.so python tools/chain_prof.py [--nodes 16000]
     python tools/chain_prof.py --no-stamps        # launch times of the shipped library"""
@@ -42,7 +42,7 @@ def main():
         _lib.call("gine_chain_bwd_folded2", P(dh0), P(u), P(wfold), P(wfold2), P(dt), P(dr), N,
                   D, F, st)
 
-    for name, fn in (("forward (F2D)", fwd), ("backward (B2D)", bwd)):
+    for name, fn in (("forward", fwd), ("backward", bwd)):
         for _ in range(3):
             fn()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

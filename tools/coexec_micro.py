@@ -1,6 +1,6 @@
 """Do two backward launches that only feed the optimizer overlap when they run together?
 Times the DeepSet weight-gradient kernel (gine_deepset_bwd, slab left) and the dense-chain
-weight-gradient engine (gine_chain_wgrad, slab left) at the cfg2 shape: each alone, back to
+weight-gradient engine (gine_chain_wgrad_folded2, slab left) at the cfg2 shape: each alone, back to
 back on one stream, and on two streams at once (eager launches, HIP events).
     python tools/coexec_micro.py [--nodes 16000] [--reps 20]"""
 import argparse
@@ -30,7 +30,7 @@ def main():
     parts = ctypes.c_int32(0)
     _lib.call("gine_deepset_bwd_num_partials", N, H, ctypes.byref(parts))
     ds_slab = torch.empty(parts.value * (H * F + H), device=dev)
-    t = {k: torch.randn(N, H, device=dev) for k in ("dh0", "r", "s", "u", "e", "de", "dt", "ds")}
+    t = {k: torch.randn(N, H, device=dev) for k in ("dh0", "r", "u", "dt")}
     x = torch.randn(N, F, device=dev)
     fl = ctypes.c_size_t(0)
     _lib.call("gine_chain_bwd_slab_floats", N, H, F, ctypes.byref(fl))
@@ -41,9 +41,8 @@ def main():
                   H, s.cuda_stream)
 
     def ch_wgrad(s):
-        _lib.call("gine_chain_wgrad", P(t["dh0"]), P(x), P(t["r"]), P(t["s"]), P(t["u"]),
-                  P(t["e"]), P(t["de"]), P(t["dt"]), P(t["ds"]), P(ch_slab), None, None, 11.0,
-                  None, None, None, None, None, None, N, H, F, s.cuda_stream)
+        _lib.call("gine_chain_wgrad_folded2", P(t["dh0"]), P(x), P(t["r"]), P(t["u"]),
+                  P(t["dt"]), P(ch_slab), None, None, N, H, F, s.cuda_stream)
 
     s0 = torch.cuda.current_stream(dev)
     s1 = torch.cuda.Stream(dev)
