@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GINE_ABI_VERSION 9  /* 2: adamw step-state query, gine_count_valid, window plan slot/edge_begin;
+#define GINE_ABI_VERSION 10 /* 2: adamw step-state query, gine_count_valid, window plan slot/edge_begin;
                               3: gine_deepset_bwd_num_partials takes the hidden width;
                               4: bn_acc grows two grid-barrier words (gine_mp_fwd_layer);
                               5: grid-barrier failure count (gine_bn_acc_barrier_failures_index),
@@ -41,7 +41,8 @@ extern "C" {
                               8: gine_mp_fwd_layer can also run the output head (gine_layer_head);
                               9: the seven entry points of the singly folded dense chain are removed
                                  (the doubly folded form is the chain; the unfolded one stays as
-                                 the tests' comparator) */
+                                 the tests' comparator);
+                              10: gine_mp_fwd_layer_eval (the eval-mode layer in one launch) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -436,6 +437,28 @@ int gine_mp_fwd_layer(const float* x, const int32_t* in_rowptr, const int32_t* i
                       int64_t num_nodes, int32_t channels, int32_t max_in_degree, int32_t flags,
                       int32_t epilogue, const int32_t* tile_windows, int32_t window_rows,
                       const gine_layer_head* head, void* stream);
+/* The layer forward in EVAL mode in ONE launch (ABI 10; eval.py:57-69 model.eval() forward of
+ * models/gnn.py:41-44): BatchNorm from the running statistics is a per-channel affine map
+ * known before the launch (alpha = gamma * invstd(running_var, bn_eps), shift = beta -
+ * running_mean * alpha, the eval branch of gine_bn_fwd_finalize), so no tile depends on
+ * another -- no statistics, no bn_acc, no grid barrier, hence no residency requirement, no
+ * size limit beyond num_nodes * 512 < 2^32 (GINE_ERR_TOO_LARGE) and no failure word.
+ * Replaces gine_mp_fwd_mlp1 + gine_bn_fwd_finalize + gine_mlp_fwd2 (+ gine_head_fwd[_count]
+ * with head != NULL) with the same bits in y, raw, pred and count_parts.  Nothing else is
+ * written: no z, a1, mask, bn_save, partials or running statistics.  With a head, y may be
+ * NULL (predictions only).  gamma / beta may be NULL.
+ * Any num_nodes >= 1 (0: GINE_OK, nothing launched); channels = 128 (GINE_ERR_DIM);
+ * max_in_degree <= GINE_MP_FUSED_MAX_DEGREE, flags (GINE_MP_LIN_MULADD) and epilogue as for
+ * gine_mp_fwd_layer (GINE_ERR_INVALID).  A workgroup walks its 32-row tiles in rounds of two,
+ * so the grid is free: max_workgroups caps it (0: one workgroup per tile up to one per CU). */
+int gine_mp_fwd_layer_eval(const float* x, const int32_t* in_rowptr, const int32_t* in_src,
+                           const float* in_attr, const float* lin_w, const float* lin_b,
+                           const float* eps, const float* w1, const float* b1,
+                           const float* gamma, const float* beta, const float* running_mean,
+                           const float* running_var, float bn_eps, const float* w2,
+                           const float* b2, float* y, int64_t num_nodes, int32_t channels,
+                           int32_t max_in_degree, int32_t flags, int32_t epilogue,
+                           const gine_layer_head* head, int32_t max_workgroups, void* stream);
 /* The layer window plan of a graph (built once per graph, like its CSRs): for every 32-row
  * tile of destinations, tile_windows[2T] = first row and tile_windows[2T + 1] = number of rows
  * of the run [lo, lo + rows) holding the tile's own rows and all their in-neighbours (int32

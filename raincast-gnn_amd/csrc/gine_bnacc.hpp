@@ -290,4 +290,18 @@ __device__ __forceinline__ void bn_finish_channel(const BnFwdParams& q, int D, i
   q.bn_save[3 * D + c] = shift_f;
 }
 
+// Eval mode: (alpha, shift) of channel c from the running statistics -- the arithmetic of
+// gine_bn_fwd_finalize's eval branch (no batch statistics, nothing written to memory).
+__device__ __forceinline__ void bn_eval_channel(const BnFwdParams& q, int c, float* alpha_out,
+                                                float* shift_out) {
+  const double mean = (double)q.rmean[c];
+  const double var = (double)q.rvar[c];
+  const double invstd = 1.0 / sqrt(var + (double)q.bn_eps);
+  const double g = q.gamma ? (double)q.gamma[c] : 1.0;
+  const double bt = q.beta ? (double)q.beta[c] : 0.0;
+  const double alpha = g * invstd;
+  *alpha_out = (float)alpha;
+  *shift_out = (float)(bt - mean * alpha);
+}
+
 }  // namespace gine

@@ -8,8 +8,9 @@ The compute path is the C-ABI library ``_native/libgine_hip.so`` (include/gine_h
 from . import _lib
 from .graph import GineGraph, get_graph, graph_cache
 from .nn import GINEConv
+from .inference import Predictor
 
-__all__ = ["GINEConv", "GineGraph", "get_graph", "graph_cache", "native_library"]
+__all__ = ["GINEConv", "GineGraph", "Predictor", "get_graph", "graph_cache", "native_library"]
 
 
 def native_library():

@@ -18,12 +18,13 @@ LIB_PATH = os.environ.get("GINE_HIP_LIB", os.path.join(_HERE, "_native", "libgin
 
 GINE_OK = 0
 GINE_ERR_INVALID, GINE_ERR_DIM = 1, 2
+GINE_ERR_TOO_LARGE = 4
 GINE_ERR_HIP_BASE = 1000
 GINE_MP_BWD_SELF = 1
 GINE_MP_LIN_MULADD = 2
 EPI_NONE, EPI_RELU, EPI_RESIDUAL_RELU = 0, 1, 2
 LOSS_NORMAL, LOSS_MIXED_NORMAL, LOSS_MIXED, LOSS_MIXED_U = 0, 1, 2, 3
-ABI_VERSION = 9
+ABI_VERSION = 10
 COUNT_PARTS = 64  # GINE_COUNT_PARTS
 
 _c_void_p = ctypes.c_void_p
@@ -99,6 +100,9 @@ _SIGNATURES = {
     "gine_mp_fwd_layer": [_c_void_p] * 18 + [_f32, _f32, _i32] + [_c_void_p] * 4
                          + [_i64, _i32, _i32, _i32, _i32, _c_void_p, _i32,
                             ctypes.POINTER(LayerHead), _c_void_p],
+    "gine_mp_fwd_layer_eval": [_c_void_p] * 13 + [_f32] + [_c_void_p] * 3
+                              + [_i64, _i32, _i32, _i32, _i32, ctypes.POINTER(LayerHead), _i32,
+                                 _c_void_p],
     "gine_graph_plan_layer_windows": [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p,
                                       _c_void_p],
     "gine_mp_fwd_layer_windows_fit": [_i32, _i32, ctypes.POINTER(_i32)],

@@ -17,26 +17,45 @@ from .data import restore_node_order
 
 
 @torch.no_grad()
-def predict_model(model: torch.nn.Module, batches: Iterable, device) -> torch.Tensor:
+def predict_model(model: torch.nn.Module, batches: Iterable, device,
+                  fused: bool = False) -> torch.Tensor:
     """eval.py:57-69: eval mode, one forward per batch, predictions concatenated on the CPU
-    (rows in the collated order of each batch, whatever order the batch is stored in)."""
+    (rows in the collated order of each batch, whatever order the batch is stored in).
+    ``fused``: the forward of the model's :class:`raincast_gnn.inference.Predictor` (one launch
+    per GINE layer; same bits), kept on the model (``inference.predictor_for``) so that later
+    calls replay what earlier ones captured.  Only batches that come back as the same
+    device-resident ``edge_index`` / ``edge_attr`` tensors are replayed; host batches are new
+    tensors after every ``.to(device)`` and run eager."""
     model.eval()
+    if fused:
+        from .inference import predictor_for
+        fwd = predictor_for(model)
+    else:
+        fwd = model
     # batches in the engine's station order come back in the reference (collated) order
-    out = [restore_node_order(model(b.to(device)), b).cpu() for b in batches]
+    out = [restore_node_order(fwd(b.to(device)), b).cpu() for b in batches]
     return torch.cat(out, dim=0)
 
 
-def predict_ensemble(make_model, checkpoints, batches, device) -> torch.Tensor:
+def predict_ensemble(make_model, checkpoints, batches, device,
+                     fused: bool = False) -> torch.Tensor:
     """eval.py:178-212: one model per checkpoint (state_dict path or dict), predictions
-    averaged over checkpoints.  ``batches`` is re-iterated per checkpoint."""
-    batches = list(batches)
+    averaged over checkpoints.  ``batches`` is re-iterated per checkpoint.
+    ``fused``: one model and its ``Predictor`` for all checkpoints, each loaded into the model
+    in place (``load_state_dict`` copies into the parameters' storage, which the captured
+    forward reads).  The batches are moved to the device once, so every checkpoint sees the
+    same tensors: per distinct edge list (up to the Predictor's ``max_captures``) one eager
+    call and one capture, then a replay per further checkpoint."""
+    batches = [b.to(device) for b in batches] if fused else list(batches)
     preds = []
+    model = None
     for ck in checkpoints:
-        model = make_model().to(device)
+        if not fused or model is None:
+            model = make_model().to(device)
         state = torch.load(ck, map_location=device, weights_only=True) if isinstance(ck, str) \
             else ck
         model.load_state_dict(state)
-        preds.append(predict_model(model, batches, device))
+        preds.append(predict_model(model, batches, device, fused))
     if len(preds) == 1:
         return preds[0]
     return torch.stack(preds, dim=0).mean(dim=0)

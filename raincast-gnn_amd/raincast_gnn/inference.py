@@ -1,0 +1,219 @@
+"""Inference on the engine: the eval-mode GINE layer in one launch, and a captured forward.
+
+In eval mode BatchNorm is a per-channel affine map known before the launch, so a whole GINE
+layer -- message passing, Linear, BatchNorm, ReLU, Linear, ResGnn's epilogue and, on the last
+layer, the output head -- is one launch of ``gine_mp_fwd_layer_eval`` with no grid barrier
+(include/gine_hip.h).  It writes the layer's output (or only the predictions) and nothing a
+backward would need, and gives the bits of the separate eval launches ``GINEConv`` makes.
+
+* :func:`layer_eval` / :func:`layer_eval_ok` -- that launch for one ``GINEConv``, and whether
+  it applies.
+* :class:`Predictor` -- ``model.eval()(batch)`` under ``no_grad`` with every layer on it
+  (front + one launch per layer), captured into one HIP graph per batch shape.
+
+``evaluate.predict_model(..., fused=True)`` and ``predict_ensemble(..., fused=True)`` run on a
+``Predictor``; the ensemble loads every checkpoint into one model in place, so one capture
+serves all of them.
+"""
+from __future__ import annotations
+
+import ctypes
+from collections import OrderedDict
+
+import torch
+
+from . import _lib
+from . import head as fused_head
+from .data import GraphBatch
+from .functional import EPI_RELU, EPI_RESIDUAL_RELU, edge_linear_flag
+from .graph import get_graph
+from .linear import Linear as RowLinear
+
+CHANNELS = 128  # gine_mp_fwd_layer_eval's only width
+
+
+def layer_eval_ok(conv, x: torch.Tensor, graph) -> bool:
+    """``gine_mp_fwd_layer_eval`` applies to ``conv`` on ``x``: the fusable node MLP at D = 128
+    on a HIP device, an edge Linear(1, D) and edge attributes, every in-degree within
+    GINE_MP_FUSED_MAX_DEGREE, and a BatchNorm in eval mode that has running statistics."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2
+            and x.dtype == torch.float32 and x.size(1) == CHANNELS):
+        return False
+    if not conv._fusable(x):
+        return False
+    lin = conv.lin
+    if lin is None or lin.in_features != 1 or lin.out_features != CHANNELS or lin.bias is None:
+        return False
+    deg = graph.max_in_degree
+    if (graph.in_attr is None or deg is None or deg > _lib.MP_FUSED_MAX_DEGREE
+            or graph.num_nodes != x.size(0) or x.size(0) * CHANNELS * 4 >= 1 << 32):
+        return False
+    bn = conv.nn[1]
+    return not bn.training and bn.running_mean is not None and bn.running_var is not None
+
+
+def layer_eval(conv, x: torch.Tensor, graph, epilogue: int, head=None, max_workgroups: int = 0,
+               with_y: bool = True):
+    """One eval-mode layer of ``conv`` on ``x`` in one launch: ``y = epilogue(nn(z))`` with
+    BatchNorm from its running statistics (no autograd; the caller checked
+    :func:`layer_eval_ok`).  ``head``: a ``head.HeadPlan`` whose raw / pred (and valid-target
+    counts) the launch also writes; then ``with_y=False`` skips ``y`` and returns None.
+    ``max_workgroups``: a cap on the grid (0: the kernel's choice).  Allocates ``y`` only."""
+    x = x.contiguous()
+    N, D = x.shape
+    y = torch.empty_like(x) if (with_y or head is None) else None
+    if N == 0:
+        return y
+    l1, bn, _, l2 = conv.nn
+    hargs = head.args(N, D, x.device) if head is not None else None
+    if head is not None and hargs is None:
+        raise ValueError("layer_eval: the head plan was made for another shape or device")
+    # the operands as they lie in memory (host time: no views or copies of contiguous
+    # parameters); the list keeps a rare contiguous copy alive until the launch is enqueued
+    ops = [_dense(t) for t in (conv.lin.weight, conv.lin.bias, conv.eps, l1.weight, l1.bias,
+                               bn.weight, bn.bias, bn.running_mean, bn.running_var, l2.weight,
+                               l2.bias)]
+    lw, lb, ep, w1, b1, g, bt, rm, rv, w2, b2 = (_lib.ptr(t) for t in ops)
+    _lib.call("gine_mp_fwd_layer_eval", x.data_ptr(), graph.in_rowptr.data_ptr(),
+              graph.in_src.data_ptr(), graph.in_attr.data_ptr(), lw, lb, ep, w1, b1, g, bt, rm,
+              rv, bn.eps, w2, b2, _lib.ptr(y), N, D, graph.max_in_degree, edge_linear_flag(),
+              epilogue, ctypes.byref(hargs) if hargs is not None else None, max_workgroups,
+              _lib.stream_handle(x.device))
+    return y
+
+
+def _dense(t):
+    return t if t is None or t.is_contiguous() else t.detach().contiguous()
+
+
+class Predictor:
+    """``predictor(batch)`` = ``model.eval()(batch)`` under ``no_grad``: the ``[N, K]``
+    predictions in the batch's stored order, with the same bits.
+
+    The front runs on the DeepSet and chain kernels ``GNN`` uses; every GINE layer is one
+    ``gine_mp_fwd_layer_eval`` launch, the last one carrying the output head (front + one launch
+    per layer).  A layer or head the launch does not cover runs the path ``GNN.forward`` takes,
+    and a model that is not on a HIP device is simply called.
+
+    ``capture=True`` (HIP devices): after ``warmup`` eager calls with one (``edge_index``
+    object, N), the forward for it is captured into one HIP graph and replayed with ``x`` and
+    ``ensemble`` copied into its static inputs.  The edge list is recognised by identity, so a
+    loader has to hand out the same device-resident ``edge_index`` / ``edge_attr`` tensors again
+    to be replayed (``batching.DeviceDataset`` does; host batches moved with ``.to(device)`` are
+    new tensors every time and always run eager).  At most ``max_captures`` edge lists are
+    tracked, least recently used first out.  A capture owns what it reads: its static inputs
+    and the ``GineGraph`` CSRs, whatever the graph cache does later.  The graphs read the
+    parameters' storage, so ``load_state_dict`` (an in-place copy) is seen by the next replay;
+    if any parameter's or buffer's storage pointer changed, the captures are dropped."""
+
+    def __init__(self, model: torch.nn.Module, capture: bool = True, warmup: int = 1,
+                 max_captures: int = 8):
+        self.model = model.eval()
+        self.capture, self.warmup, self.max_captures = capture, warmup, max_captures
+        # (id(edge_index), N) -> [edge_index, edge_attr, calls, capture | None]; the slot holds
+        # the tensors, so an id stays theirs while it is a key
+        self._slots: OrderedDict = OrderedDict()
+        self._ptrs = None
+
+    @property
+    def _graphs(self) -> dict:
+        """The live captures: key -> (HIP graph, static batch, output, GineGraphs held)."""
+        return {k: s[3] for k, s in self._slots.items() if s[3] is not None}
+
+    # -- the forward ---------------------------------------------------------------------
+    def _forward(self, batch, keep: list | None = None) -> torch.Tensor:
+        """``keep``: a list the GineGraphs this forward reads are appended to."""
+        m = self.model
+        if not batch.x.is_cuda or not self._is_gnn():
+            return m(batch)
+        stack = m.conv.convolutions
+        x = m._front(batch).float()
+        ei, ea = batch.edge_index, batch.edge_attr.float()
+        kind = fused_head.loss_kind(m.postprocess.loss, m.postprocess.grad_u)
+        head_ok = (type(m.aggr) in (RowLinear, torch.nn.Linear)  # (GNN.forward's condition)
+                   and fused_head.fusable(x, m.aggr, kind))
+        last = len(stack) - 1
+        by_flow = {}  # one cache lookup per forward, not per layer
+        for i, conv in enumerate(stack):
+            epi = EPI_RELU if i == 0 else EPI_RESIDUAL_RELU
+            graph = None
+            if conv.lin is not None:
+                graph = by_flow.get(conv.flow)
+                if graph is None:
+                    graph = by_flow[conv.flow] = get_graph(ei, ea, x.size(0), conv.flow)
+                    if keep is not None:
+                        keep.append(graph)
+            if graph is not None and layer_eval_ok(conv, x, graph):
+                if i == last and head_ok:  # predictions only: the last layer's y is not stored
+                    plan = fused_head.plan(x, m.aggr, kind, None)
+                    layer_eval(conv, x, graph, epi, head=plan, with_y=False)
+                    return plan.pred
+                x = layer_eval(conv, x, graph, epi)
+            elif i == 0:
+                x = conv.forward_relu(x, ei, ea)
+            else:
+                x = conv.forward_residual_relu(x, ei, ea)
+        if head_ok:
+            return fused_head.head(x, m.aggr, kind, None)
+        return m.postprocess(m.aggr(x))
+
+    def _is_gnn(self) -> bool:
+        """The model has models.GNN's parts (front, GINE stack, aggr, postprocess)."""
+        m = self.model
+        return (getattr(getattr(m, "conv", None), "convolutions", None) is not None
+                and all(hasattr(m, a) for a in ("_front", "aggr", "postprocess")))
+
+    def _storage_ptrs(self) -> tuple:
+        m = self.model
+        return tuple(t.data_ptr() for t in m.parameters()) + tuple(
+            t.data_ptr() for t in m.buffers())
+
+    @torch.no_grad()
+    def __call__(self, batch: GraphBatch) -> torch.Tensor:
+        self.model.eval()
+        if not self.capture or not batch.x.is_cuda or not self._is_gnn():
+            return self._forward(batch)  # (another model's forward is never captured)
+        ptrs = self._storage_ptrs()
+        if ptrs != self._ptrs:  # a parameter moved: what was captured reads freed storage
+            self._slots.clear()
+            self._ptrs = ptrs
+        key = (id(batch.edge_index), batch.x.size(0))
+        slot = self._slots.get(key)
+        if slot is None or slot[0] is not batch.edge_index or slot[1] is not batch.edge_attr:
+            slot = self._slots[key] = [batch.edge_index, batch.edge_attr, 0, None]
+            while len(self._slots) > max(self.max_captures, 1):
+                self._slots.popitem(last=False)
+        self._slots.move_to_end(key)
+        slot[2] += 1
+        if slot[2] <= self.warmup:
+            return self._forward(batch)
+        if slot[3] is None:
+            slot[3] = self._capture(batch)
+        graph, static, out, _ = slot[3]
+        if static.x.shape != batch.x.shape or static.ensemble.shape != batch.ensemble.shape:
+            return self._forward(batch)  # not what was captured
+        static.x.copy_(batch.x)
+        static.ensemble.copy_(batch.ensemble)
+        graph.replay()
+        return out.clone()
+
+    def _capture(self, batch) -> tuple:
+        static = GraphBatch(batch.x.clone(), batch.ensemble.clone(), batch.edge_index,
+                            batch.edge_attr, batch.y, batch.batch, batch.ptr, batch.num_graphs,
+                            dict(batch.extra))
+        self._forward(static)  # the graph's CSR and every size query exist before the capture
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        held: list = []  # the GineGraphs whose CSR pointers the captured launches carry
+        with torch.cuda.graph(graph):
+            out = self._forward(static, held)
+        return graph, static, out, held
+
+
+def predictor_for(model: torch.nn.Module) -> Predictor:
+    """The model's own :class:`Predictor` (made on first use and kept on the model, outside its
+    state_dict), so that repeated ``predict_model(..., fused=True)`` calls share its captures."""
+    pred = model.__dict__.get("_raincast_predictor")
+    if pred is None or pred.model is not model:
+        pred = model.__dict__["_raincast_predictor"] = Predictor(model)
+    return pred
