@@ -42,7 +42,8 @@ extern "C" {
                               9: the seven entry points of the singly folded dense chain are removed
                                  (the doubly folded form is the chain; the unfolded one stays as
                                  the tests' comparator);
-                              10: gine_mp_fwd_layer_eval (the eval-mode layer in one launch) */
+                              10: gine_mp_fwd_layer_eval (the eval-mode layer in one launch); later,
+                                  additive within 10: gine_mp_fwd_layer_eval_deep (any in-degree) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -459,6 +460,23 @@ int gine_mp_fwd_layer_eval(const float* x, const int32_t* in_rowptr, const int32
                            const float* b2, float* y, int64_t num_nodes, int32_t channels,
                            int32_t max_in_degree, int32_t flags, int32_t epilogue,
                            const gine_layer_head* head, int32_t max_workgroups, void* stream);
+/* gine_mp_fwd_layer_eval at ANY in-degree (additive in ABI 10; the reference's radius graphs,
+ * utils/data.py:261-284, and k = 32 plus the self loop are past GINE_MP_FUSED_MAX_DEGREE): the
+ * same launch, arguments, validation and outputs, except that max_in_degree only has to be
+ * >= 0 -- the kernel takes every row's length from in_rowptr and walks its edge list in chunks
+ * of 32 slots (csrc/gine_mpeval.hip gather_role_deep), a row's sum being the same sequence of
+ * additions in edge order.  y, raw, pred and count_parts have the bits of the separate eval
+ * launches at every degree, and of gine_mp_fwd_layer_eval where that applies.  Same LDS, grid
+ * policy and max_workgroups.  Inference only: the training forms keep the degree limit. */
+int gine_mp_fwd_layer_eval_deep(const float* x, const int32_t* in_rowptr, const int32_t* in_src,
+                                const float* in_attr, const float* lin_w, const float* lin_b,
+                                const float* eps, const float* w1, const float* b1,
+                                const float* gamma, const float* beta,
+                                const float* running_mean, const float* running_var,
+                                float bn_eps, const float* w2, const float* b2, float* y,
+                                int64_t num_nodes, int32_t channels, int32_t max_in_degree,
+                                int32_t flags, int32_t epilogue, const gine_layer_head* head,
+                                int32_t max_workgroups, void* stream);
 /* The layer window plan of a graph (built once per graph, like its CSRs): for every 32-row
  * tile of destinations, tile_windows[2T] = first row and tile_windows[2T + 1] = number of rows
  * of the run [lo, lo + rows) holding the tile's own rows and all their in-neighbours (int32

@@ -1,4 +1,5 @@
-// GINE layer forward in eval mode in one launch (gine_mp_fwd_layer_eval, D = 128).
+// GINE layer forward in eval mode in one launch (gine_mp_fwd_layer_eval, D = 128), and the
+// same at any in-degree (gine_mp_fwd_layer_eval_deep).
 #include "gine_mpmlp.hpp"
 
 namespace gine {
@@ -117,14 +118,153 @@ __device__ __forceinline__ void eval_round_matrix(const FusedArgs& A, const Laye
   __syncthreads();            // the round's LDS use is over
 }
 
+// The gather role at any in-degree (gine_mp_fwd_layer_eval_deep): gather_role<FMA, false,
+// false, false> of gine_mpmlp.hpp restated (sharing it through a flag would touch the
+// training kernels' code), with the row's edge list walked in chunks of kSlots through the
+// same nbr / attr tables.  Chunk 0 keeps the two-stage prefetch; a further chunk is loaded by
+// the half-wave that owns the rows once the chunk before it is consumed (its own table rows:
+// the wave's program order is the only synchronisation, as for chunk 0).  A pair's shorter row
+// has count 0 in its extra chunks: wholly masked, +0 added, so every row sees acc = 0, its
+// edges in CSR order, then add_scaled -- the bits of any other form.  Every address is valid
+// for every lane: an edge index is clamped to the row's last edge (0 for an empty row), a
+// masked slot holds the row itself, a row past N is N - 1.
+// Barriers: 1 + nt (the caller runs the last one), as gather_role without LAST_SYNC.
+// Neighbour rows in flight per row of the pair: a 32-slot chunk is four full steps of eight
+// (gather_role's eleven, sized for k = 10 plus the self loop, would be 11 + 11 + 10 and, with
+// the rows' first edge and in-degree kept for the further chunks, spills six registers).
+constexpr int kUD = 8;
+static_assert(kSlots % kUD == 0, "a full chunk is a whole number of steps");
+template <bool FMA>
+__device__ __forceinline__ void gather_role_deep(const FusedArgs& A, FusedLds& L,
+                                                 const TileSeq& ts, int nt) {
+  static_assert(kRowsPerHalf == 2, "one pair of rows per half-wave");
+  const int p = per_round((int)threadIdx.x) - kMatThreads;
+  const int hw = p >> 5, t = p & 31;
+  const int N = A.N;
+  const uint32_t qb = (uint32_t)t * 16u;
+  const char* xb = reinterpret_cast<const char*>(A.x);
+  RowptrStage rp;
+  EdgeStage es;
+  int32_t ebeg[kRowsPerHalf];  // the staged tile's first edge and whole in-degree per row
+  int edeg[kRowsPerHalf];
+#pragma unroll
+  for (int i = 0; i < kRowsPerHalf; ++i) {
+    rp.beg[i] = rp.end[i] = 0;
+    es.nbr[i] = 0;
+    es.attr[i] = 0.f;
+    es.cnt[i] = 0;
+    ebeg[i] = 0;
+    edeg[i] = 0;
+  }
+  auto row_of = [&](int T, int i) { return T * kTileRows + hw + kHalves * i; };
+  auto clamp_row = [&](int n) { return n < N ? n : N - 1; };
+  auto issue_rowptr = [&](int T) {  // -> rp (no wait)
+#pragma unroll
+    for (int i = 0; i < kRowsPerHalf; ++i) {
+      const int n = clamp_row(row_of(T, i));
+      rp.beg[i] = A.rowptr[n];
+      rp.end[i] = A.rowptr[n + 1];
+    }
+  };
+  auto issue_edges = [&](int T) {  // rp (of tile T, arrived) -> es: chunk 0 (no wait)
+#pragma unroll
+    for (int i = 0; i < kRowsPerHalf; ++i) {
+      const int deg = row_of(T, i) < N ? max(rp.end[i] - rp.beg[i], 0) : 0;
+      const int cnt = min(deg, kSlots);
+      const int e = cnt > 0 ? rp.beg[i] + min(t, cnt - 1) : 0;  // always a valid index
+      es.nbr[i] = A.nbr[e];
+      es.attr[i] = A.attr[e];
+      es.cnt[i] = cnt;
+      ebeg[i] = rp.beg[i];
+      edeg[i] = deg;
+    }
+  };
+  const f4v lw = ld_f4v(reinterpret_cast<const char*>(A.lin_w), qb);
+  const f4v lb = ld_f4v(reinterpret_cast<const char*>(A.lin_b), qb);
+  const float ope = 1.0f + A.eps[0];
+  if (nt > 0) {
+    issue_rowptr(ts.at(0));
+    issue_edges(ts.at(0));
+  }
+  if (nt > 1) issue_rowptr(ts.at(1));
+  __syncthreads();
+
+  for (int it = 0; it < nt; ++it) {
+    const int T = ts.at(it);
+    float* sz = L.z[it & 1];
+    int cnt[kRowsPerHalf], deg[kRowsPerHalf];
+    int32_t beg[kRowsPerHalf];
+#pragma unroll
+    for (int i = 0; i < kRowsPerHalf; ++i) {
+      L.nbr[hw][i][t] = t < es.cnt[i] ? es.nbr[i] : clamp_row(row_of(T, i));
+      L.attr[hw][i][t] = es.attr[i];
+      cnt[i] = es.cnt[i];
+      beg[i] = ebeg[i];
+      deg[i] = edeg[i];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (it + 1 < nt) issue_edges(ts.at(it + 1));
+    if (it + 2 < nt) issue_rowptr(ts.at(it + 2));
+    f4v self[kRowsPerHalf], acc[kRowsPerHalf];
+#pragma unroll
+    for (int i = 0; i < kRowsPerHalf; ++i) {
+      self[i] = ld_f4v(xb, (uint32_t)clamp_row(row_of(T, i)) * kRowBytes + qb);
+      acc[i] = f4v_zero();
+    }
+    const int mdeg = max(deg[0], deg[1]);
+    for (int c0 = 0;; c0 += kSlots) {  // the chunk holding edges c0 .. c0 + kSlots - 1
+      const int m = max(cnt[0], cnt[1]);
+      for (int j0 = 0; j0 < m; j0 += kUD) {
+        f4v r0[kUD], r1[kUD];
+        float a0[kUD], a1v[kUD];
+#pragma unroll
+        for (int u = 0; u < kUD; ++u) {
+          const int j = min(j0 + u, kSlots - 1);
+          r0[u] = ld_f4v(xb, (uint32_t)L.nbr[hw][0][j] * kRowBytes + qb);
+          r1[u] = ld_f4v(xb, (uint32_t)L.nbr[hw][1][j] * kRowBytes + qb);
+          a0[u] = L.attr[hw][0][j];
+          a1v[u] = L.attr[hw][1][j];
+        }
+#pragma unroll
+        for (int u = 0; u < kUD; ++u) {
+          edge_acc<FMA>(acc[0], r0[u], a0[u], lw, lb, j0 + u < cnt[0]);
+          edge_acc<FMA>(acc[1], r1[u], a1v[u], lw, lb, j0 + u < cnt[1]);
+        }
+      }
+      if (c0 + kSlots >= mdeg) break;
+      __builtin_amdgcn_wave_barrier();  // this chunk's reads done before the next one's writes
+#pragma unroll
+      for (int i = 0; i < kRowsPerHalf; ++i) {
+        const int cn = max(0, min(deg[i] - (c0 + kSlots), kSlots));
+        // slot t of the next chunk, clamped to the row's last edge (an empty row: edge 0)
+        const int e = deg[i] > 0 ? beg[i] + min(c0 + kSlots + t, deg[i] - 1) : 0;
+        const int32_t nb = A.nbr[e];
+        L.attr[hw][i][t] = A.attr[e];
+        L.nbr[hw][i][t] = t < cn ? nb : clamp_row(row_of(T, i));
+        cnt[i] = cn;
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int i = 0; i < kRowsPerHalf; ++i) {
+      const int r = hw + kHalves * i;
+      const f4v zv = add_scaled(acc[i], ope, self[i]);
+      *reinterpret_cast<f4v*>(&sz[r * kLD + 4 * t]) = zv;
+    }
+    __builtin_amdgcn_wave_barrier();  // edge-list reads done before the next tile's writes
+    __syncthreads();
+  }
+}
+
 // One round of the gather waves: phase A's gather, W2's staging, their share of the relu
 // planes, then the epilogue (and head) of each tile beside the matrix waves' next chain.
-template <bool FMA, int EPI>
+template <bool FMA, int EPI, bool DEEP = false>
 __device__ __forceinline__ void eval_round_gather(const FusedArgs& A, const LayerArgs& B,
                                                   LayerLds& L, const TileSeq& rs, int nt) {
   constexpr int kG = kThreads - kMatThreads;
   constexpr int kW2Per = kD * kD4 / kG;
-  gather_role<FMA, false, false, false>(A, L.f, rs, nt);
+  if constexpr (DEEP) gather_role_deep<FMA>(A, L.f, rs, nt);
+  else gather_role<FMA, false, false, false>(A, L.f, rs, nt);
   const int tidr = per_round(threadIdx.x);
   const int p = tidr - kMatThreads;  // 0 .. 511
   const int eq = p & 31, er = p >> 5;
@@ -293,24 +433,87 @@ __global__ __launch_bounds__(kThreads, 1) void k_mp_fwd_layer_eval(FusedArgs A, 
   }
 }
 
+// k_mp_fwd_layer_eval at any in-degree (gine_mp_fwd_layer_eval_deep): the gather waves run
+// gather_role_deep; all else is the kernel above restated (a body shared as a function changes
+// the instruction streams of the six instantiations above), and must be kept in step with it.
+template <bool FMA, int EPI>
+__global__ __launch_bounds__(kThreads, 1) void k_mp_fwd_layer_eval_deep(FusedArgs A,
+                                                                        LayerArgs B) {
+  __shared__ __attribute__((aligned(16))) LayerLds L;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const bool mat = wave < kMatThreads / kWave;
+  // the row GEMM's XCD-contiguous map where every XCD has a workgroup, else a plain stride
+  const TileSeq ts = gridDim.x >= (unsigned)kNumXcd
+                         ? tile_seq(A.num_tiles, blockIdx.x, gridDim.x)
+                         : TileSeq{(int)blockIdx.x, A.num_tiles, (int)gridDim.x};
+  const int nall = ts.count();
+  float* const hwl = L.hd;
+  uint32_t* const cwl = reinterpret_cast<uint32_t*>(hwl + kHC);
+
+  // ---- once: alpha | shift, the head's weights and the valid-target counts ----
+  const int p0 = tid - kMatThreads;  // (gather waves: 0 .. 511)
+  if (tid < GINE_COUNT_PARTS) cwl[tid] = 0;
+  if (!mat && p0 < kD) bn_eval_channel(B.q, p0, &L.bn[p0], &L.bn[kD + p0]);
+  if (!mat && B.hk) {
+    if (p0 < B.hk * kD4)
+      *reinterpret_cast<float4*>(&hwl[4 * p0]) =
+          *reinterpret_cast<const float4*>(B.hd.weight + 4 * p0);
+    else if (p0 < B.hk * kD4 + B.hk)
+      hwl[kHB + p0 - B.hk * kD4] = B.hd.bias[p0 - B.hk * kD4];
+  }
+  if (B.hk && B.hd.count_parts) {  // (k_mp_fwd_layer's count: integer sums, any order)
+    __syncthreads();
+    if (!mat) {
+      const int64_t chunk = ((int64_t)A.N + GINE_COUNT_PARTS - 1) / GINE_COUNT_PARTS;
+      for (int q = blockIdx.x; q < GINE_COUNT_PARTS; q += gridDim.x) {
+        const int64_t lo = (int64_t)q * chunk, hi = min(lo + chunk, (int64_t)A.N);
+        uint32_t c = 0;
+        for (int64_t i = lo + p0; i < hi; i += kThreads - kMatThreads)
+          c += B.hd.y_target[i] == B.hd.y_target[i];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+        if (tid % kWave == 0) atomicAdd(&cwl[q], c);
+      }
+    }
+    __syncthreads();
+    if (!mat) {
+      const int q = (int)blockIdx.x + p0 * (int)gridDim.x;
+      if (q < GINE_COUNT_PARTS) B.hd.count_parts[q] = cwl[q];
+    }
+  }
+  // The roles keep to their own branch for the whole round (one barrier sequence each, as in
+  // phase A): what one role holds in registers -- W2's planes, the residual rows -- is then
+  // no live value of the other's code.
+  for (int r0 = 0; r0 < nall; r0 += kLayerTiles) {
+    const TileSeq rs{ts.at(r0), min(ts.end, ts.at(r0 + kLayerTiles)), ts.step};
+    const int nt = rs.count();  // 1 .. kLayerTiles
+    if (mat) eval_round_matrix(A, B, L, rs, nt, wave);
+    else eval_round_gather<FMA, EPI, true>(A, B, L, rs, nt);
+  }
+}
+
 }  // namespace
 }  // namespace gine
 
 using namespace gine;
 
-extern "C" int gine_mp_fwd_layer_eval(const float* x, const int32_t* in_rowptr,
-                                      const int32_t* in_src, const float* in_attr,
-                                      const float* lin_w, const float* lin_b, const float* eps,
-                                      const float* w1, const float* b1, const float* gamma,
-                                      const float* beta, const float* running_mean,
-                                      const float* running_var, float bn_eps, const float* w2,
-                                      const float* b2, float* y, int64_t num_nodes,
-                                      int32_t channels, int32_t max_in_degree, int32_t flags,
-                                      int32_t epilogue, const gine_layer_head* head,
-                                      int32_t max_workgroups, void* stream) {
+namespace {
+// Both entries: validation before any HIP call, then one launch.  DEEP: k_mp_fwd_layer_eval_deep,
+// whose only degree condition is max_in_degree >= 0 (the rows' lengths come from in_rowptr).
+template <bool DEEP>
+int layer_eval_launch(const float* x, const int32_t* in_rowptr, const int32_t* in_src,
+                      const float* in_attr, const float* lin_w, const float* lin_b,
+                      const float* eps, const float* w1, const float* b1, const float* gamma,
+                      const float* beta, const float* running_mean, const float* running_var,
+                      float bn_eps, const float* w2, const float* b2, float* y,
+                      int64_t num_nodes, int32_t channels, int32_t max_in_degree, int32_t flags,
+                      int32_t epilogue, const gine_layer_head* head, int32_t max_workgroups,
+                      void* stream) {
   if (channels != kD) return GINE_ERR_DIM;
   if ((flags & ~GINE_MP_LIN_MULADD) != 0) return GINE_ERR_INVALID;
-  if (max_in_degree < 0 || max_in_degree > GINE_MP_FUSED_MAX_DEGREE) return GINE_ERR_INVALID;
+  if (max_in_degree < 0 || (!DEEP && max_in_degree > GINE_MP_FUSED_MAX_DEGREE))
+    return GINE_ERR_INVALID;
   if (epilogue < GINE_EPI_NONE || epilogue > GINE_EPI_RESIDUAL_RELU) return GINE_ERR_INVALID;
   if (num_nodes < 0 || max_workgroups < 0) return GINE_ERR_INVALID;
   if (!x || !in_rowptr || !in_src || !in_attr || !lin_w || !lin_b || !eps || !w1 || !b1 ||
@@ -349,9 +552,15 @@ extern "C" int gine_mp_fwd_layer_eval(const float* x, const int32_t* in_rowptr,
                                 0.f, bn_eps, 0},
                     nullptr, 0, 0, head ? *head : gine_layer_head{}, hk};
   const bool fma = !(flags & GINE_MP_LIN_MULADD);
-#define EVAL_LAUNCH(F_, E_)                                                               \
-  hipLaunchKernelGGL((k_mp_fwd_layer_eval<F_, E_>), dim3((unsigned)grid), dim3(kThreads), 0, \
-                     s, A, B)
+#define EVAL_LAUNCH(F_, E_)                                                              \
+  do {                                                                                   \
+    if (DEEP)                                                                            \
+      hipLaunchKernelGGL((k_mp_fwd_layer_eval_deep<F_, E_>), dim3((unsigned)grid),       \
+                         dim3(kThreads), 0, s, A, B);                                    \
+    else                                                                                 \
+      hipLaunchKernelGGL((k_mp_fwd_layer_eval<F_, E_>), dim3((unsigned)grid),            \
+                         dim3(kThreads), 0, s, A, B);                                    \
+  } while (0)
   switch (epilogue) {
     case GINE_EPI_NONE:
       if (fma) EVAL_LAUNCH(true, EPI_OUT); else EVAL_LAUNCH(false, EPI_OUT);
@@ -365,4 +574,37 @@ extern "C" int gine_mp_fwd_layer_eval(const float* x, const int32_t* in_rowptr,
 #undef EVAL_LAUNCH
   GINE_LAUNCH_STATUS();
   return GINE_OK;
+}
+}  // namespace
+
+extern "C" int gine_mp_fwd_layer_eval(const float* x, const int32_t* in_rowptr,
+                                      const int32_t* in_src, const float* in_attr,
+                                      const float* lin_w, const float* lin_b, const float* eps,
+                                      const float* w1, const float* b1, const float* gamma,
+                                      const float* beta, const float* running_mean,
+                                      const float* running_var, float bn_eps, const float* w2,
+                                      const float* b2, float* y, int64_t num_nodes,
+                                      int32_t channels, int32_t max_in_degree, int32_t flags,
+                                      int32_t epilogue, const gine_layer_head* head,
+                                      int32_t max_workgroups, void* stream) {
+  return layer_eval_launch<false>(x, in_rowptr, in_src, in_attr, lin_w, lin_b, eps, w1, b1, gamma,
+                                  beta, running_mean, running_var, bn_eps, w2, b2, y, num_nodes,
+                                  channels, max_in_degree, flags, epilogue, head, max_workgroups,
+                                  stream);
+}
+
+extern "C" int gine_mp_fwd_layer_eval_deep(const float* x, const int32_t* in_rowptr,
+                                           const int32_t* in_src, const float* in_attr,
+                                           const float* lin_w, const float* lin_b, const float* eps,
+                                           const float* w1, const float* b1, const float* gamma,
+                                           const float* beta, const float* running_mean,
+                                           const float* running_var, float bn_eps, const float* w2,
+                                           const float* b2, float* y, int64_t num_nodes,
+                                           int32_t channels, int32_t max_in_degree, int32_t flags,
+                                           int32_t epilogue, const gine_layer_head* head,
+                                           int32_t max_workgroups, void* stream) {
+  return layer_eval_launch<true>(x, in_rowptr, in_src, in_attr, lin_w, lin_b, eps, w1, b1, gamma,
+                                  beta, running_mean, running_var, bn_eps, w2, b2, y, num_nodes,
+                                  channels, max_in_degree, flags, epilogue, head, max_workgroups,
+                                  stream);
 }

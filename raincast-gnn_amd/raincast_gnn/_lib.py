@@ -103,6 +103,9 @@ _SIGNATURES = {
     "gine_mp_fwd_layer_eval": [_c_void_p] * 13 + [_f32] + [_c_void_p] * 3
                               + [_i64, _i32, _i32, _i32, _i32, ctypes.POINTER(LayerHead), _i32,
                                  _c_void_p],
+    "gine_mp_fwd_layer_eval_deep": [_c_void_p] * 13 + [_f32] + [_c_void_p] * 3
+                                   + [_i64, _i32, _i32, _i32, _i32, ctypes.POINTER(LayerHead),
+                                      _i32, _c_void_p],
     "gine_graph_plan_layer_windows": [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p,
                                       _c_void_p],
     "gine_mp_fwd_layer_windows_fit": [_i32, _i32, ctypes.POINTER(_i32)],

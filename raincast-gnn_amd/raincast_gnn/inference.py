@@ -7,7 +7,9 @@ layer, the output head -- is one launch of ``gine_mp_fwd_layer_eval`` with no gr
 backward would need, and gives the bits of the separate eval launches ``GINEConv`` makes.
 
 * :func:`layer_eval` / :func:`layer_eval_ok` -- that launch for one ``GINEConv``, and whether
-  it applies.
+  it applies (every in-degree within GINE_MP_FUSED_MAX_DEGREE).
+* :func:`layer_eval_deep` / :func:`layer_eval_deep_ok` -- ``gine_mp_fwd_layer_eval_deep``: the
+  same launch at any in-degree (radius graphs, k = 32 plus the self loop), same bits.
 * :class:`Predictor` -- ``model.eval()(batch)`` under ``no_grad`` with every layer on it
   (front + one launch per layer), captured into one HIP graph per batch shape.
 
@@ -30,12 +32,18 @@ from .graph import get_graph
 from .linear import Linear as RowLinear
 
 CHANNELS = 128  # gine_mp_fwd_layer_eval's only width
+# The largest N at which the Predictor takes the deep launch by default (None: no limit).  Past
+# some N each workgroup walks many rounds and stages W1 / W2 again in every one, and the
+# separate launches win.  Measured with tools/infer_bench.py --force-deep --separate (DESIGN.md
+# 6a, profiles/r08_infer_bench_*.txt): up to N = 40,000 (in-degree 33) the Predictor with the
+# deep launch is faster than with the separate launches in both forms, and than
+# model.eval()(batch) in at least one; at N = 64,000 (radius graph, in-degree <= 45) it is 2.5 %
+# slower than the separate launches and at N = 80,000 (cfg5) it ties them.
+DEEP_MAX_NODES = 40_000
 
 
-def layer_eval_ok(conv, x: torch.Tensor, graph) -> bool:
-    """``gine_mp_fwd_layer_eval`` applies to ``conv`` on ``x``: the fusable node MLP at D = 128
-    on a HIP device, an edge Linear(1, D) and edge attributes, every in-degree within
-    GINE_MP_FUSED_MAX_DEGREE, and a BatchNorm in eval mode that has running statistics."""
+def _layer_eval_common(conv, x: torch.Tensor, graph) -> bool:
+    """Every condition of the one-launch eval layer but the in-degree."""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2
             and x.dtype == torch.float32 and x.size(1) == CHANNELS):
         return False
@@ -44,12 +52,25 @@ def layer_eval_ok(conv, x: torch.Tensor, graph) -> bool:
     lin = conv.lin
     if lin is None or lin.in_features != 1 or lin.out_features != CHANNELS or lin.bias is None:
         return False
-    deg = graph.max_in_degree
-    if (graph.in_attr is None or deg is None or deg > _lib.MP_FUSED_MAX_DEGREE
+    if (graph.in_attr is None or graph.max_in_degree is None
             or graph.num_nodes != x.size(0) or x.size(0) * CHANNELS * 4 >= 1 << 32):
         return False
     bn = conv.nn[1]
     return not bn.training and bn.running_mean is not None and bn.running_var is not None
+
+
+def layer_eval_ok(conv, x: torch.Tensor, graph) -> bool:
+    """``gine_mp_fwd_layer_eval`` applies to ``conv`` on ``x``: the fusable node MLP at D = 128
+    on a HIP device, an edge Linear(1, D) and edge attributes, every in-degree within
+    GINE_MP_FUSED_MAX_DEGREE, and a BatchNorm in eval mode that has running statistics."""
+    return (_layer_eval_common(conv, x, graph)
+            and graph.max_in_degree <= _lib.MP_FUSED_MAX_DEGREE)
+
+
+def layer_eval_deep_ok(conv, x: torch.Tensor, graph) -> bool:
+    """``gine_mp_fwd_layer_eval_deep`` applies: :func:`layer_eval_ok`'s conditions without the
+    degree limit."""
+    return _layer_eval_common(conv, x, graph)
 
 
 def layer_eval(conv, x: torch.Tensor, graph, epilogue: int, head=None, max_workgroups: int = 0,
@@ -59,6 +80,19 @@ def layer_eval(conv, x: torch.Tensor, graph, epilogue: int, head=None, max_workg
     :func:`layer_eval_ok`).  ``head``: a ``head.HeadPlan`` whose raw / pred (and valid-target
     counts) the launch also writes; then ``with_y=False`` skips ``y`` and returns None.
     ``max_workgroups``: a cap on the grid (0: the kernel's choice).  Allocates ``y`` only."""
+    return _layer_launch("gine_mp_fwd_layer_eval", conv, x, graph, epilogue, head,
+                         max_workgroups, with_y)
+
+
+def layer_eval_deep(conv, x: torch.Tensor, graph, epilogue: int, head=None,
+                    max_workgroups: int = 0, with_y: bool = True):
+    """:func:`layer_eval` at any in-degree (``gine_mp_fwd_layer_eval_deep``; the caller checked
+    :func:`layer_eval_deep_ok`): same arguments, same contract, same bits."""
+    return _layer_launch("gine_mp_fwd_layer_eval_deep", conv, x, graph, epilogue, head,
+                         max_workgroups, with_y)
+
+
+def _layer_launch(entry: str, conv, x, graph, epilogue, head, max_workgroups, with_y):
     x = x.contiguous()
     N, D = x.shape
     y = torch.empty_like(x) if (with_y or head is None) else None
@@ -74,7 +108,7 @@ def layer_eval(conv, x: torch.Tensor, graph, epilogue: int, head=None, max_workg
                                bn.weight, bn.bias, bn.running_mean, bn.running_var, l2.weight,
                                l2.bias)]
     lw, lb, ep, w1, b1, g, bt, rm, rv, w2, b2 = (_lib.ptr(t) for t in ops)
-    _lib.call("gine_mp_fwd_layer_eval", x.data_ptr(), graph.in_rowptr.data_ptr(),
+    _lib.call(entry, x.data_ptr(), graph.in_rowptr.data_ptr(),
               graph.in_src.data_ptr(), graph.in_attr.data_ptr(), lw, lb, ep, w1, b1, g, bt, rm,
               rv, bn.eps, w2, b2, _lib.ptr(y), N, D, graph.max_in_degree, edge_linear_flag(),
               epilogue, ctypes.byref(hargs) if hargs is not None else None, max_workgroups,
@@ -92,8 +126,10 @@ class Predictor:
 
     The front runs on the DeepSet and chain kernels ``GNN`` uses; every GINE layer is one
     ``gine_mp_fwd_layer_eval`` launch, the last one carrying the output head (front + one launch
-    per layer).  A layer or head the launch does not cover runs the path ``GNN.forward`` takes,
-    and a model that is not on a HIP device is simply called.
+    per layer).  On a graph past that launch's degree limit the layers run
+    ``gine_mp_fwd_layer_eval_deep`` instead, up to ``DEEP_MAX_NODES`` nodes.  A layer or head
+    neither launch covers runs the path ``GNN.forward`` takes, and a model that is not on a HIP
+    device is simply called.
 
     ``capture=True`` (HIP devices): after ``warmup`` eager calls with one (``edge_index``
     object, N), the forward for it is captured into one HIP graph and replayed with ``x`` and
@@ -143,12 +179,19 @@ class Predictor:
                     graph = by_flow[conv.flow] = get_graph(ei, ea, x.size(0), conv.flow)
                     if keep is not None:
                         keep.append(graph)
-            if graph is not None and layer_eval_ok(conv, x, graph):
+            run = None
+            if graph is not None:
+                if layer_eval_ok(conv, x, graph):
+                    run = layer_eval
+                elif ((DEEP_MAX_NODES is None or x.size(0) <= DEEP_MAX_NODES)
+                      and layer_eval_deep_ok(conv, x, graph)):
+                    run = layer_eval_deep
+            if run is not None:
                 if i == last and head_ok:  # predictions only: the last layer's y is not stored
                     plan = fused_head.plan(x, m.aggr, kind, None)
-                    layer_eval(conv, x, graph, epi, head=plan, with_y=False)
+                    run(conv, x, graph, epi, head=plan, with_y=False)
                     return plan.pred
-                x = layer_eval(conv, x, graph, epi)
+                x = run(conv, x, graph, epi)
             elif i == 0:
                 x = conv.forward_relu(x, ei, ea)
             else:
