@@ -43,7 +43,8 @@ extern "C" {
                                  (the doubly folded form is the chain; the unfolded one stays as
                                  the tests' comparator);
                               10: gine_mp_fwd_layer_eval (the eval-mode layer in one launch); later,
-                                  additive within 10: gine_mp_fwd_layer_eval_deep (any in-degree) */
+                                  additive within 10: gine_mp_fwd_layer_eval_deep (any in-degree),
+                                  gine_forecast_prob / _quantile / _score(_partials) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -594,6 +595,50 @@ int gine_crps_head_fwd_grad(const float* pred, const float* y, int64_t num_nodes
                             float* dh, float* head_slab, void* stream);
 int gine_crps_head_grad_job(int64_t num_nodes, int32_t channels, int32_t kind,
                             const float* head_slab, float* dw, float* db, gine_grad_job* job);
+
+/* ------------------------------------------------------------------------------------
+ * The predictive distribution those losses score, over pred [N, K] fp32 (kind: GINE_LOSS_*);
+ * every result fp64.  c = censoring point, z(x) = (x - mu) / sigma, Phi = normal cdf:
+ *   NORMAL        F(x) = Phi(z)
+ *   MIXED_NORMAL  F(x) = 0 for x < c, p + (1 - p) Phi(z) for x >= c (an atom P_c = F(c) at c)
+ *   MIXED(_U)     as MIXED_NORMAL below u; for x >= u  m_u + (1 - m_u) G((x - u) / sigma_u),
+ *                 m_u = p + (1 - p) Phi(z(u)), G(t) = 1 - (1 + xi t)^(-1/xi); u fixed (MIXED)
+ *                 or the row's own (MIXED_U)
+ * Defined for c < u and 0 < xi < 1: GINE_ERR_INVALID, before any HIP call, for a fixed
+ * u <= c or xi outside (0, 1) (the two MIXED kinds) and for c >= 0 with MIXED_U (its u lies in
+ * (0, 2.12)); for a bad kind, flag, negative size or NULL operand too.  At most 2^24
+ * thresholds or levels (GINE_ERR_TOO_LARGE).  num_nodes = 0: GINE_OK, nothing launched.  One
+ * launch each, no allocation, no host synchronisation (capturable).
+ * gine_forecast_prob: out[n, t] = F(x[t]) = P(Y <= x[t]); with GINE_FORECAST_UPPER
+ *   P(Y > x[t]), formed from erfc and the tail power (never 1 - F), exactly 1 below c.
+ *   x: device pointer, num_x values.
+ * gine_forecast_quantile: out[n, j] = inf{x : F(x) >= level[j]}: c for a level up to P_c,
+ *   +inf at level 1, c (NORMAL: -inf) at level 0, NaN for a level outside [0, 1] or NaN.
+ *   With GINE_FORECAST_UPPER the levels are exceedance probabilities s = 1 - q, used without
+ *   forming 1 - s (return levels down to s = 1e-12).
+ * gine_forecast_score: the scores of targets y [N] fp32 (NaN = missing) in one launch.  Per
+ *   row the CRPS (of the distribution: where(y < u, ...) for MIXED_U too, not the sigmoid
+ *   blend of training) and the PIT interval [F(y-), F(y)] = [pit_lo, pit_hi], which is
+ *   [0, P_c] at the atom and one point elsewhere; NaN in all three for a NaN target.  Per
+ *   threshold brier[t] = mean over valid rows of (P(Y > x[t]) - 1{y > x[t]})^2, and valid[0] =
+ *   their number (NaN and 0 when there is none).  For the PIT and the Brier score a target at
+ *   or below c is the atom (fp32 log 0.01 lies below the fp64 one).  crps_rows, pit_lo,
+ *   pit_hi, valid may be NULL; num_x = 0 is allowed.  partials:
+ *   gine_forecast_score_partials() doubles; sums in a fixed order (same bits every run);
+ *   ticket as for gine_crps_fwd (zeroed once, left at 0, calls sharing it must not overlap).
+ * ---------------------------------------------------------------------------------- */
+#define GINE_FORECAST_UPPER 1
+int gine_forecast_prob(const float* pred, int64_t num_nodes, int32_t kind, double u, double xi,
+                       double c, const double* x, int32_t num_x, int32_t flags, double* out,
+                       void* stream);
+int gine_forecast_quantile(const float* pred, int64_t num_nodes, int32_t kind, double u,
+                           double xi, double c, const double* level, int32_t num_levels,
+                           int32_t flags, double* out, void* stream);
+int gine_forecast_score_partials(int64_t num_nodes, int32_t num_x, size_t* count);
+int gine_forecast_score(const float* pred, const float* y, int64_t num_nodes, int32_t kind,
+                        double u, double xi, double c, const double* x, int32_t num_x,
+                        double* crps_rows, double* pit_lo, double* pit_hi, double* brier,
+                        double* valid, double* partials, uint32_t* ticket, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Weight/bias gradient of a plain Linear y = x W^T + b over many rows (the DeepSet,

@@ -9,8 +9,10 @@ from . import _lib
 from .graph import GineGraph, get_graph, graph_cache
 from .nn import GINEConv
 from .inference import Predictor
+from .forecast import Forecast, ForecastScore, pit_sample
 
-__all__ = ["GINEConv", "GineGraph", "Predictor", "get_graph", "graph_cache", "native_library"]
+__all__ = ["Forecast", "ForecastScore", "GINEConv", "GineGraph", "Predictor", "get_graph",
+           "graph_cache", "native_library", "pit_sample"]
 
 
 def native_library():

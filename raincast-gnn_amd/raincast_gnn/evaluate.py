@@ -64,3 +64,13 @@ def predict_ensemble(make_model, checkpoints, batches, device,
 def ensemble_crps(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor):
     """eval.py:216-218: the CRPS of the averaged predictions under the model's loss."""
     return model.loss_fn.crps(preds, targets)
+
+
+def verify(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor, thresholds,
+           unit: str = "mm"):
+    """Verification of the predictions as forecasts (:mod:`raincast_gnn.forecast`): per-row
+    CRPS and PIT interval, and the Brier score of exceeding each threshold (``unit``: the
+    thresholds', millimetres by default; the targets are the dataset's ``log(mm + 0.01)``).
+    On a HIP device one launch; returns a :class:`raincast_gnn.forecast.ForecastScore`."""
+    from .forecast import Forecast
+    return Forecast.from_model(model, preds).score(targets, thresholds, unit=unit)
