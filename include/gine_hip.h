@@ -44,7 +44,10 @@ extern "C" {
                                  the tests' comparator);
                               10: gine_mp_fwd_layer_eval (the eval-mode layer in one launch); later,
                                   additive within 10: gine_mp_fwd_layer_eval_deep (any in-degree),
-                                  gine_forecast_prob / _quantile / _score(_partials) */
+                                  gine_forecast_prob / _quantile / _score(_partials),
+                                  gine_graph_build_ek / gine_graph_same_edges_ek and
+                                  gine_mp_fwd_ek / gine_mp_bwd_ek(_num_partials, _finalize): edge_dim
+                                  up to GINE_MP_MAX_EDGE_DIM and the edge_attr gradient */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -84,6 +87,23 @@ int gine_graph_build(const int64_t* edge_index, const float* edge_attr, int64_t 
 int gine_graph_same_edges(const int64_t* edge_index_a, const int64_t* edge_index_b,
                           const float* edge_attr_a, const float* edge_attr_b, int64_t num_edges,
                           int32_t* differ, void* stream);
+/* gine_graph_build for edge_attr [E, K] (row-major, 1 <= K = edge_dim <= GINE_MP_MAX_EDGE_DIM,
+ * GINE_ERR_INVALID otherwise; PyG GINEConv(edge_dim=K)): the same two stable sorts;
+ * in_attr / out_attr are [E, K], row p holding the K attributes of the edge in CSR slot p, and
+ * out_eid [E] (int32) is the position in the caller's edge list (= row of edge_attr) of the
+ * edge in out-CSR slot p -- where gine_mp_bwd_ek stores that edge's attribute gradient.
+ * Workspace: gine_graph_workspace_bytes.  edge_attr, in_attr, out_attr and out_eid are
+ * required when num_edges > 0. */
+int gine_graph_build_ek(const int64_t* edge_index, const float* edge_attr, int64_t num_nodes,
+                        int64_t num_edges, int32_t edge_dim, int32_t* in_rowptr,
+                        int32_t* in_src, float* in_attr, int32_t* out_rowptr, int32_t* out_dst,
+                        float* out_attr, int32_t* out_eid, int32_t* d_error, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* gine_graph_same_edges over edge_attr [E, edge_dim]: all 4 * edge_dim * E attribute bytes
+ * are compared (edge_attr 16-byte aligned, as there). */
+int gine_graph_same_edges_ek(const int64_t* edge_index_a, const int64_t* edge_index_b,
+                             const float* edge_attr_a, const float* edge_attr_b,
+                             int64_t num_edges, int32_t edge_dim, int32_t* differ, void* stream);
 /* the device address of pinned (page-locked) host memory (hipHostGetDevicePointer); an error
  * status when the memory is not mapped for the device. */
 int gine_host_device_ptr(void* host_ptr, void** device_ptr);
@@ -137,6 +157,49 @@ int gine_mp_bwd_side(const float* dz, const float* x, const int32_t* out_rowptr,
                      double* partials, int64_t num_nodes, int32_t channels, int32_t flags,
                      const float* wg_slab, int32_t wg_chunks, int32_t mlp_channels, float* dw1,
                      float* db1, float* dw2, float* db2, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Message passing with K = edge_dim attributes per edge, 1 <= K <= GINE_MP_MAX_EDGE_DIM
+ * (PyG GINEConv(edge_dim=K): lin = Linear(K, D)), and the gradient of the attributes.  For an
+ * edge e with attributes a_e[0..K-1], lin_w W [D, K] (lin.weight's layout) and lin_b b [D]:
+ *   e_c = b_c;  for k = 0 .. K-1:  e_c = fma(a_e[k], W[c][k], e_c)   (one rounding per term, in
+ *                                                                     this order)
+ *   m_e = relu(x[src_e] + e)    z_i = sum over in-edges of i, original edge order, of m_e
+ *                                     + (1 + eps) * x_i
+ * At K = 1 this is gine_mp_fwd's fma mode, bit for bit; there is no rounding flag.  (A CPU
+ * Linear(K, D) with K > 1 is an sgemm whose summation order is the BLAS's own: bit-identity
+ * with torch's CPU result is not defined for K > 1.)  in_attr / out_attr [E, K] and out_eid
+ * [E] as gine_graph_build_ek writes them.
+ * Backward over the out-edge CSR, dm_e = (x[src_e] + e <= 0) ? 0 : dz[dst_e]:
+ *   dx as gine_mp_bwd (flags: GINE_MP_BWD_SELF only; dres may be NULL)
+ *   partials[b] (fp64, a row of (K + 2) * D per block b): sum dm*a_k [D*K, laid out [c][k]],
+ *            sum dm [D], then the block's sum of dz*x (one value; the rest unused)
+ *   dea != NULL: dea[out_eid[p] * K + k] = sum_c dm_e[c] * W[c][k] for the edge e in slot p
+ *            (each lane's 4 channels in fp32, then a fixed butterfly over the row group;
+ *            plain stores, every edge written once: no zero-fill needed).  NULL: not computed,
+ *            and the launch is the instantiation without that code.
+ * gine_mp_bwd_ek_finalize reduces the partials in fixed block order into dlin_w [D, K],
+ * dlin_b [D], deps [1].
+ * Supported D: multiple of 4, 4 <= D <= 256 (GINE_ERR_DIM); edge_dim outside 1..8:
+ * GINE_ERR_INVALID; num_nodes * D * 4 and num_edges * K * 4 below 2^32 (GINE_ERR_TOO_LARGE);
+ * num_nodes = 0: GINE_OK, nothing launched.  All checked before any HIP call.
+ * ---------------------------------------------------------------------------------- */
+#define GINE_MP_MAX_EDGE_DIM 8
+int gine_mp_fwd_ek(const float* x, const int32_t* in_rowptr, const int32_t* in_src,
+                   const float* in_attr, const float* lin_w, const float* lin_b,
+                   const float* eps, float* z, int64_t num_nodes, int64_t num_edges,
+                   int32_t channels, int32_t edge_dim, void* stream);
+int gine_mp_bwd_ek_num_partials(int64_t num_nodes, int32_t channels, int32_t edge_dim,
+                                int32_t* num_partials);
+int gine_mp_bwd_ek(const float* dz, const float* x, const int32_t* out_rowptr,
+                   const int32_t* out_dst, const float* out_attr, const int32_t* out_eid,
+                   const float* lin_w, const float* lin_b, const float* eps, const float* dres,
+                   float* dx, float* dea, double* partials, int64_t num_nodes,
+                   int64_t num_edges, int32_t channels, int32_t edge_dim, int32_t flags,
+                   void* stream);
+int gine_mp_bwd_ek_finalize(const double* partials, int32_t num_partials, int32_t channels,
+                            int32_t edge_dim, float* dlin_w, float* dlin_b, float* deps,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Window-staged message passing (same results as gine_mp_fwd / gine_mp_bwd, bit for bit

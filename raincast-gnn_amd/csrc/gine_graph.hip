@@ -52,6 +52,21 @@ __global__ void k_gather_segment(const int32_t* __restrict__ perm,
   if (attr != nullptr) seg_attr[p] = attr[e];
 }
 
+// k_gather_segment for K attributes per edge: row p of seg_attr [E, K] = row perm[p] of attr;
+// seg_eid (the out-edge side) keeps the edge's position in the caller's list.
+__global__ void k_gather_segment_ek(const int32_t* __restrict__ perm,
+                                    const int32_t* __restrict__ other_end,
+                                    const float* __restrict__ attr, int64_t E, int K,
+                                    int32_t* __restrict__ seg_other,
+                                    float* __restrict__ seg_attr, int32_t* __restrict__ seg_eid) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= E) return;
+  const int32_t e = perm[p];
+  seg_other[p] = other_end[e];
+  if (seg_eid != nullptr) seg_eid[p] = e;
+  for (int k = 0; k < K; ++k) seg_attr[p * K + k] = attr[(int64_t)e * K + k];
+}
+
 // rowptr[i] = first position whose sorted key >= i  (lower bound), rowptr[N] = E.
 __global__ void k_rowptr(const int32_t* __restrict__ sorted_keys, int64_t E, int64_t N,
                          int32_t* __restrict__ rowptr) {
@@ -175,6 +190,78 @@ extern "C" int gine_graph_build(const int64_t* edge_index, const float* edge_att
   return GINE_OK;
 }
 
+extern "C" int gine_graph_build_ek(const int64_t* edge_index, const float* edge_attr,
+                                   int64_t num_nodes, int64_t num_edges, int32_t edge_dim,
+                                   int32_t* in_rowptr, int32_t* in_src, float* in_attr,
+                                   int32_t* out_rowptr, int32_t* out_dst, float* out_attr,
+                                   int32_t* out_eid, int32_t* d_error, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (num_nodes < 0 || num_edges < 0 || edge_dim < 1 || edge_dim > GINE_MP_MAX_EDGE_DIM)
+    return GINE_ERR_INVALID;
+  if (num_nodes >= (int64_t(1) << 31) || num_edges >= (int64_t(1) << 31))
+    return GINE_ERR_TOO_LARGE;
+  if (in_rowptr == nullptr || out_rowptr == nullptr || d_error == nullptr)
+    return GINE_ERR_INVALID;
+  if (num_edges > 0 && (edge_index == nullptr || edge_attr == nullptr || in_src == nullptr ||
+                        out_dst == nullptr || in_attr == nullptr || out_attr == nullptr ||
+                        out_eid == nullptr || workspace == nullptr))
+    return GINE_ERR_INVALID;
+  Layout L;
+  int st = plan(num_nodes, num_edges, &L);
+  if (st != GINE_OK) return st;
+  if (num_edges > 0 && workspace_bytes < L.total) return GINE_ERR_WORKSPACE;
+
+  hipStream_t s = as_stream(stream);
+  const int64_t E = num_edges, N = num_nodes;
+  const int threads = 256;
+  const unsigned ng = (unsigned)ceil_div(N + 1, threads);
+  if (E == 0) {
+    hipLaunchKernelGGL(k_rowptr, dim3(ng), dim3(threads), 0, s, (const int32_t*)nullptr,
+                       (int64_t)0, N, in_rowptr);
+    GINE_LAUNCH_STATUS();
+    hipLaunchKernelGGL(k_rowptr, dim3(ng), dim3(threads), 0, s, (const int32_t*)nullptr,
+                       (int64_t)0, N, out_rowptr);
+    GINE_LAUNCH_STATUS();
+    return GINE_OK;
+  }
+  char* ws = static_cast<char*>(workspace);
+  int32_t* src32 = reinterpret_cast<int32_t*>(ws + L.src32);
+  int32_t* dst32 = reinterpret_cast<int32_t*>(ws + L.dst32);
+  int32_t* ids = reinterpret_cast<int32_t*>(ws + L.ids);
+  int32_t* keys_out = reinterpret_cast<int32_t*>(ws + L.keys_out);
+  int32_t* perm = reinterpret_cast<int32_t*>(ws + L.perm);
+  void* temp = ws + L.temp;
+  size_t temp_bytes = L.temp_bytes;
+  const int bits = key_bits(N);
+  const unsigned eg = (unsigned)ceil_div(E, threads);
+
+  hipLaunchKernelGGL(k_split_edges, dim3(eg), dim3(threads), 0, s, edge_index, E, N, src32,
+                     dst32, ids, d_error);
+  GINE_LAUNCH_STATUS();
+
+  // In-edges: stable sort by destination.
+  GINE_RETURN_IF_HIP(hipcub::DeviceRadixSort::SortPairs(
+      temp, temp_bytes, reinterpret_cast<const uint32_t*>(dst32),
+      reinterpret_cast<uint32_t*>(keys_out), ids, perm, (int)E, 0, bits, s));
+  hipLaunchKernelGGL(k_gather_segment_ek, dim3(eg), dim3(threads), 0, s, perm, src32, edge_attr,
+                     E, (int)edge_dim, in_src, in_attr, (int32_t*)nullptr);
+  GINE_LAUNCH_STATUS();
+  hipLaunchKernelGGL(k_rowptr, dim3(ng), dim3(threads), 0, s, keys_out, E, N, in_rowptr);
+  GINE_LAUNCH_STATUS();
+
+  // Out-edges: stable sort by source; the slot -> edge id map is the sort's permutation.
+  temp_bytes = L.temp_bytes;
+  GINE_RETURN_IF_HIP(hipcub::DeviceRadixSort::SortPairs(
+      temp, temp_bytes, reinterpret_cast<const uint32_t*>(src32),
+      reinterpret_cast<uint32_t*>(keys_out), ids, perm, (int)E, 0, bits, s));
+  hipLaunchKernelGGL(k_gather_segment_ek, dim3(eg), dim3(threads), 0, s, perm, dst32, edge_attr,
+                     E, (int)edge_dim, out_dst, out_attr, out_eid);
+  GINE_LAUNCH_STATUS();
+  hipLaunchKernelGGL(k_rowptr, dim3(ng), dim3(threads), 0, s, keys_out, E, N, out_rowptr);
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // Content check of a fresh edge list against a cached one (the drop-in path: train.py:62
 // copies the batch to the device every step, so edge_index is a new tensor each time while
@@ -231,6 +318,20 @@ extern "C" int gine_graph_same_edges(const int64_t* edge_index_a, const int64_t*
   int st = launch_same(edge_index_a, edge_index_b, 16 * num_edges, differ, s);
   if (st != GINE_OK || edge_attr_a == nullptr) return st;
   return launch_same(edge_attr_a, edge_attr_b, 4 * num_edges, differ, s);
+}
+
+extern "C" int gine_graph_same_edges_ek(const int64_t* edge_index_a,
+                                        const int64_t* edge_index_b, const float* edge_attr_a,
+                                        const float* edge_attr_b, int64_t num_edges,
+                                        int32_t edge_dim, int32_t* differ, void* stream) {
+  if (num_edges < 0 || !differ || edge_dim < 1 || edge_dim > GINE_MP_MAX_EDGE_DIM)
+    return GINE_ERR_INVALID;
+  if (edge_attr_a == nullptr || edge_attr_b == nullptr) return num_edges == 0 ? GINE_OK
+                                                                              : GINE_ERR_INVALID;
+  hipStream_t s = as_stream(stream);
+  const int st = launch_same(edge_index_a, edge_index_b, 16 * num_edges, differ, s);
+  if (st != GINE_OK) return st;
+  return launch_same(edge_attr_a, edge_attr_b, 4 * (int64_t)edge_dim * num_edges, differ, s);
 }
 
 extern "C" int gine_host_device_ptr(void* host_ptr, void** device_ptr) {

@@ -63,6 +63,8 @@ class LayerHead(ctypes.Structure):
 
 GRAD_JOB_MP, GRAD_JOB_SLAB, GRAD_MAX_JOBS = 1, 2, 12
 MP_FUSED_MAX_DEGREE = 32  # GINE_MP_FUSED_MAX_DEGREE
+MP_MAX_EDGE_DIM = 8  # GINE_MP_MAX_EDGE_DIM
+MP_EK_MAX_CHANNELS = 256  # gine_mp_fwd_ek / gine_mp_bwd_ek: one float4 per lane
 _job_p = ctypes.POINTER(GradJob)
 WINDOW_LDS_BYTES = 80 * 1024
 
@@ -73,6 +75,14 @@ _SIGNATURES = {
                          _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size, _c_void_p],
     "gine_graph_same_edges": [_c_void_p] * 4 + [_i64, _c_void_p, _c_void_p],
     "gine_host_device_ptr": [_c_void_p, ctypes.POINTER(_c_void_p)],
+    "gine_graph_build_ek": [_c_void_p, _c_void_p, _i64, _i64, _i32] + [_c_void_p] * 9
+                           + [_size, _c_void_p],
+    "gine_graph_same_edges_ek": [_c_void_p] * 4 + [_i64, _i32, _c_void_p, _c_void_p],
+    "gine_mp_fwd_ek": [_c_void_p] * 8 + [_i64, _i64, _i32, _i32, _c_void_p],
+    "gine_mp_bwd_ek_num_partials": [_i64, _i32, _i32, ctypes.POINTER(_i32)],
+    "gine_mp_bwd_ek": [_c_void_p] * 13 + [_i64, _i64, _i32, _i32, _i32, _c_void_p],
+    "gine_mp_bwd_ek_finalize": [_c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                _c_void_p],
     "gine_mp_fwd": [_c_void_p] * 8 + [_i64, _i32, _i32, _c_void_p],
     "gine_mp_bwd_num_partials": [_i64, _i32, ctypes.POINTER(_i32)],
     "gine_mp_bwd": [_c_void_p] * 11 + [_i64, _i32, _i32, _c_void_p],

@@ -55,12 +55,26 @@ def _finish(row: np.ndarray, col: np.ndarray, dist_vals: np.ndarray, n: int):
     return edge_index, edge_attr
 
 
-def build_edge_index_and_attr(dist_mat: np.ndarray, max_dist: float):
-    """Radius graph exactly as utils/data.py:261-284 builds it."""
+def build_edge_index_and_attr(dist_mat: np.ndarray, max_dist: float, extra=None):
+    """Radius graph exactly as utils/data.py:261-284 builds it.  ``extra``: a sequence of
+    [N, N] arrays of further edge features (altitude difference, bearing, ...): column 1 + j of
+    ``edge_attr`` [E, 1 + len(extra)] is ``extra[j][row, col]`` for the distance edges and 0
+    for the self loops (GINEConv(edge_dim=1 + len(extra)))."""
     D = dist_mat.copy()
     np.fill_diagonal(D, np.inf)
     row, col = np.where(D <= max_dist)
-    return _finish(row, col, D[row, col], dist_mat.shape[0])
+    edge_index, edge_attr = _finish(row, col, D[row, col], dist_mat.shape[0])
+    if not extra:
+        return edge_index, edge_attr
+    n = dist_mat.shape[0]
+    cols = [edge_attr]
+    for j, m in enumerate(extra):
+        m = np.asarray(m)
+        if m.shape != dist_mat.shape:
+            raise ValueError(f"extra[{j}] has shape {m.shape}, expected {dist_mat.shape}")
+        vals = torch.tensor(m[row, col], dtype=torch.float32)
+        cols.append(torch.cat([vals, torch.zeros(n, dtype=torch.float32)]).unsqueeze(-1))
+    return edge_index, torch.cat(cols, dim=1)
 
 
 def knn_edge_index_and_attr(dist_mat: np.ndarray, k: int):

@@ -98,10 +98,32 @@ def _as_vec(p: torch.Tensor) -> torch.Tensor:
     return p.detach().reshape(-1).contiguous()
 
 
-def mp_forward(x, graph, lin_w, lin_b, eps, lin_flag=None):
+def is_wide(graph) -> bool:
+    """The graph runs the K-wide gather kernels (gine_mp_fwd_ek / gine_mp_bwd_ek): edge_dim > 1,
+    or an edge_dim = 1 graph built with ``out_eid`` for the edge_attr gradient."""
+    return getattr(graph, "out_eid", None) is not None
+
+
+def _check_wide(graph, D: int) -> None:
+    if D % 4 or D > _lib.MP_EK_MAX_CHANNELS:
+        raise NotImplementedError(
+            f"edge_dim={graph.edge_dim} (or an edge_attr gradient) with {D} channels: the K-wide "
+            f"message passing takes multiples of 4 up to {_lib.MP_EK_MAX_CHANNELS} channels")
+
+
+def mp_forward(x, graph, lin_w, lin_b, eps, lin_flag=None, wide=False):
+    """``lin_w``: [D] at edge_dim 1, [D, K] (lin.weight's layout, flattened or not) above.
+    Graphs with edge_dim > 1 or ``out_eid`` run gine_mp_fwd_ek (the fma chain, no rounding
+    flag); ``wide=True`` runs it on a plain edge_dim = 1 graph too (tests, tools)."""
     N, D = x.shape
     z = torch.empty_like(x)
     if N == 0:
+        return z
+    if wide or is_wide(graph):
+        _check_wide(graph, D)
+        call("gine_mp_fwd_ek", ptr(x), ptr(graph.in_rowptr), ptr(graph.in_src),
+             ptr(graph.in_attr), ptr(lin_w), ptr(lin_b), ptr(eps), ptr(z), N, graph.num_edges,
+             D, graph.edge_dim, _lib.stream_handle(x.device))
         return z
     flag = edge_linear_flag() if lin_flag is None else lin_flag
     plan = graph.window_plan("in", D)
@@ -116,8 +138,14 @@ def mp_forward(x, graph, lin_w, lin_b, eps, lin_flag=None):
 
 
 def mp_backward(dz, x, graph, lin_w, lin_b, eps, dres=None, self_term=True, lin_flag=None,
-                params=(None, None, None), side=None, engine=None, jobs=None):
-    """Returns (dx, dlin_w, dlin_b, deps); ``params`` = the (lin.weight, lin.bias, eps)
+                params=(None, None, None), side=None, engine=None, jobs=None,
+                edge_grad=False, wide=False):
+    """Returns (dx, dlin_w, dlin_b, deps) -- and with ``edge_grad=True`` a fifth entry, the
+    gradient [E, K] of the caller's edge_attr (graphs with ``out_eid`` only).  Graphs with
+    edge_dim > 1 or ``out_eid`` (and any edge_dim = 1 graph with ``wide=True``) run
+    gine_mp_bwd_ek and finish with gine_mp_bwd_ek_finalize at once (dlin_w is [D * K], in
+    lin.weight's layout); ``side`` / ``engine`` / ``jobs`` do not apply there.
+    ``params`` = the (lin.weight, lin.bias, eps)
     Parameters, whose gradients then go straight to their flat-buffer slices if any.
     ``side`` = (slab, chunks, D, dw1, db1, dw2, db2): a node-MLP weight-gradient slab left
     by gine_mlp_bwd1_wgrad, reduced by extra workgroups of the same launch.
@@ -128,6 +156,10 @@ def mp_backward(dz, x, graph, lin_w, lin_b, eps, dres=None, self_term=True, lin_
     finish launch, when the reduction is not deferred to the end of the backward."""
     N, D = x.shape
     dev = x.device
+    if wide or edge_grad or is_wide(graph):
+        assert side is None and engine is None
+        return _mp_backward_ek(dz, x, graph, lin_w, lin_b, eps, dres, self_term, params,
+                               edge_grad)
     dx = torch.empty_like(x)
     p_w, p_b, p_e = params
     dlw = grad_out(p_w, (D,), dev) if p_w is not None else torch.empty(D, device=dev)
@@ -182,11 +214,62 @@ def mp_backward(dz, x, graph, lin_w, lin_b, eps, dres=None, self_term=True, lin_
     return dx, dlw, dlb, deps
 
 
+def _mp_backward_ek(dz, x, graph, lin_w, lin_b, eps, dres, self_term, params, edge_grad):
+    """mp_backward on the K-wide kernels: one gine_mp_bwd_ek launch (the instantiation with the
+    edge gradient only when asked for) and its finish, written straight into the flat-buffer
+    slices when the parameters have them (no deferral to the end-of-backward batch)."""
+    N, D = x.shape
+    dev = x.device
+    K, E = graph.edge_dim, graph.num_edges
+    _check_wide(graph, D)
+    dx = torch.empty_like(x)
+    p_w, p_b, p_e = params
+    dlw = grad_out(p_w, (D * K,), dev) if p_w is not None else torch.empty(D * K, device=dev)
+    dlb = grad_out(p_b, (D,), dev) if p_b is not None else torch.empty(D, device=dev)
+    deps = grad_out(p_e, (1,), dev) if p_e is not None else torch.empty(1, device=dev)
+    dea = None
+    if edge_grad:
+        if graph.out_eid is None:
+            raise ValueError("the edge_attr gradient needs a graph built with out_eid "
+                             "(get_graph(..., with_eid=True) at edge_dim 1)")
+        dea = torch.empty(E, K, device=dev)  # every edge is one out-CSR slot: fully written
+    if N == 0:
+        out = (dx, dlw.zero_(), dlb.zero_(), deps.zero_())
+        return out + (dea,) if edge_grad else out
+    stream = _lib.stream_handle(dev)
+    P = _count3("gine_mp_bwd_ek_num_partials", N, D, K)
+    partials = torch.empty(P, (K + 2) * D, dtype=torch.float64, device=dev)
+    call("gine_mp_bwd_ek", ptr(dz), ptr(x), ptr(graph.out_rowptr), ptr(graph.out_dst),
+         ptr(graph.out_attr), ptr(graph.out_eid), ptr(lin_w), ptr(lin_b), ptr(eps), ptr(dres),
+         ptr(dx), ptr(dea) if E > 0 else None, ptr(partials), N, E, D, K,
+         _lib.GINE_MP_BWD_SELF if self_term else 0, stream)
+    call("gine_mp_bwd_ek_finalize", ptr(partials), P, D, K, ptr(dlw), ptr(dlb), ptr(deps),
+         stream)
+    out = (dx, dlw, dlb, deps)
+    return out + (dea,) if edge_grad else out
+
+
+def _count3(fn: str, n: int, d: int, k: int) -> int:
+    key = (fn, n, d, k)
+    v = _COUNTS.get(key)
+    if v is None:
+        out = ctypes.c_int32(0)
+        call(fn, n, d, k, ctypes.byref(out))
+        v = _COUNTS[key] = int(out.value)
+    return v
+
+
+def _wants_edge_grad(edge_attr) -> bool:
+    return edge_attr is not None and edge_attr.requires_grad
+
+
 class GineMessagePassing(torch.autograd.Function):
-    """z = sum_{e: dst_e = i} relu(x[src_e] + a_e * W_e + b_e) + (1 + eps) * x_i."""
+    """z = sum_{e: dst_e = i} relu(x[src_e] + lin(a_e)) + (1 + eps) * x_i.  ``edge_attr``: the
+    tensor the graph was built from, passed when its gradient is wanted (the values the kernels
+    read are the graph's own copy)."""
 
     @staticmethod
-    def forward(ctx, x, lin_w, lin_b, eps, graph):
+    def forward(ctx, x, lin_w, lin_b, eps, graph, edge_attr=None):
         x = x.contiguous()
         lw, lb, ep = _as_vec(lin_w), _as_vec(lin_b), eps.detach().contiguous()
         z = mp_forward(x, graph, lw, lb, ep)
@@ -194,14 +277,18 @@ class GineMessagePassing(torch.autograd.Function):
         ctx.graph = graph
         ctx.lin_w_shape = lin_w.shape
         ctx.params = (lin_w, lin_b, eps)
+        ctx.ea_shape = edge_attr.shape if _wants_edge_grad(edge_attr) else None
         return z
 
     @staticmethod
     def backward(ctx, dz):
         x, lw, lb, ep = ctx.saved_tensors
-        dx, dlw, dlb, deps = mp_backward(dz.contiguous(), x, ctx.graph, lw, lb, ep,
-                                         params=ctx.params)
-        return dx, dlw.view(ctx.lin_w_shape), dlb, deps.view_as(ep), None
+        eg = ctx.ea_shape is not None and ctx.needs_input_grad[5]
+        out = mp_backward(dz.contiguous(), x, ctx.graph, lw, lb, ep, params=ctx.params,
+                          edge_grad=eg)
+        dx, dlw, dlb, deps = out[:4]
+        dea = out[4].view(ctx.ea_shape) if eg else None
+        return dx, dlw.view(ctx.lin_w_shape), dlb, deps.view_as(ep), None, dea
 
 
 class BnConfig:
@@ -235,6 +322,8 @@ def fused_forward_ok(graph, N: int, D: int) -> bool:
     if mode == "0" or (N > FUSED_MAX_NODES and mode != "all"):
         return False
     deg = graph.max_in_degree
+    if is_wide(graph):  # K edge attributes: the gather kernels of gine_mpek.hip only
+        return False
     return (D == 128 and N > 0 and graph.in_attr is not None and deg is not None
             and deg <= _lib.MP_FUSED_MAX_DEGREE and graph.window_plan("in", D) is None)
 
@@ -242,7 +331,7 @@ def fused_forward_ok(graph, N: int, D: int) -> bool:
 def engine_in_mp_ok(graph, D: int) -> bool:
     """gine_mp_bwd_win_mlp_wgrad applies: D = 64 or 128 and a 32-channel window plan for
     the backward (options.ENGINE_IN_MP = False keeps the engine in the dz launch)."""
-    if not options.ENGINE_IN_MP or D not in (64, 128):
+    if not options.ENGINE_IN_MP or D not in (64, 128) or is_wide(graph):
         return False
     plan = graph.window_plan("out", D)
     return plan is not None and plan.slice_channels == 32
@@ -400,7 +489,7 @@ class GineLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, lin_w, lin_b, eps, w1, b1, gamma, beta, w2, b2, graph, bn, epilogue,
-                head=None):
+                head=None, edge_attr=None):
         x = x.contiguous()
         N, D = x.shape
         dev = x.device
@@ -485,6 +574,7 @@ class GineLayer(torch.autograd.Function):
         ctx.bn_acc_bwd = bn_accumulator(bn, D, dev, "bwd") if options.BN_ACC_BWD else None
         ctx.params = (lin_w, lin_b, eps, w1, b1, gamma, beta, w2, b2)
         ctx.shapes = (lin_w.shape, gamma is not None)
+        ctx.ea_shape = edge_attr.shape if _wants_edge_grad(edge_attr) else None
         return y
 
     @staticmethod
@@ -549,7 +639,9 @@ class GineLayer(torch.autograd.Function):
                  None, N, D, epi, stream)
         dres = dy if epi == EPI_RESIDUAL_RELU else None
         jobs = None
-        if deferrable or use_engine:
+        wide = is_wide(ctx.graph)
+        if deferrable or use_engine or wide:
+            # (the K-wide message passing has no side reduction: its slab takes this route)
             # only the optimizer reads dW1/db1/dW2/db2: the slab is reduced by a batch launch
             # (the end-of-backward one when deferrable), off the message passing's path
             per = D * D + D
@@ -566,12 +658,15 @@ class GineLayer(torch.autograd.Function):
             side = None
         else:  # reduced by extra workgroups of the message-passing backward launch
             side = (slab, C, D, dw1, db1, dw2, db2)
-        dx, dlw, dlb, deps = mp_backward(dz, x, ctx.graph, lw, lb, ep, dres=dres,
-                                         params=(p_lw, p_lb, p_eps), side=side, engine=engine,
-                                         jobs=jobs)
+        eg = wide and ctx.ea_shape is not None and ctx.needs_input_grad[14]
+        out = mp_backward(dz, x, ctx.graph, lw, lb, ep, dres=dres,
+                          params=(p_lw, p_lb, p_eps), side=side, engine=engine, jobs=jobs,
+                          edge_grad=eg)
+        dx, dlw, dlb, deps = out[:4]
+        dea = out[4].view(ctx.ea_shape) if eg else None
         if jobs:  # this layer's slab and message-passing finish in one launch
             arr = (_lib.GradJob * len(jobs))(*[j for j, _ in jobs])
             call("gine_grad_finalize_batch", arr, len(jobs), stream)
         lin_w_shape, affine = ctx.shapes
         return (dx, dlw.view(lin_w_shape), dlb, deps.view_as(ep), dw1, db1, dgamma, dbeta,
-                dw2, db2, None, None, None, None)
+                dw2, db2, None, None, None, None, dea)

@@ -99,14 +99,21 @@ def plan_windows(rowptr: torch.Tensor, nbr: torch.Tensor, num_nodes: int, device
 
 
 class GineGraph:
-    """Stable CSR (by destination) + CSR (by source) of one edge list on one device."""
+    """Stable CSR (by destination) + CSR (by source) of one edge list on one device.
+
+    ``edge_attr`` [E] / [E, 1] (``edge_dim`` 1: gine_graph_build, today's path) or [E, K],
+    2 <= K <= 8 (gine_graph_build_ek: ``in_attr`` / ``out_attr`` are [E, K], and ``out_eid``
+    [E] holds each out-CSR slot's position in the caller's edge list, where the backward stores
+    that edge's attribute gradient).  ``with_eid``: the K = 1 graph from the wide builder too,
+    for the edge_attr gradient at K = 1.  A graph with ``out_eid`` runs the K-wide gather
+    kernels only: no window plans, no layer windows, no fused forward."""
 
     __slots__ = ("num_nodes", "num_edges", "device", "in_rowptr", "in_src", "in_attr",
                  "out_rowptr", "out_dst", "out_attr", "_error", "_checked", "_windows",
-                 "max_in_degree", "_ext_opts", "layer_windows")
+                 "max_in_degree", "_ext_opts", "layer_windows", "edge_dim", "out_eid")
 
     def __init__(self, edge_index: torch.Tensor, edge_attr: torch.Tensor | None,
-                 num_nodes: int, flow: str = "source_to_target"):
+                 num_nodes: int, flow: str = "source_to_target", with_eid: bool = False):
         _lib.require_device(edge_index, "GineGraph")
         self._ext_opts = {}  # torch_ext's per-size option cache
         if edge_index.dim() != 2 or edge_index.size(0) != 2:
@@ -114,10 +121,16 @@ class GineGraph:
         if flow not in ("source_to_target", "target_to_source"):
             raise ValueError(f"unknown flow '{flow}'")
         E = edge_index.size(1)
-        if edge_attr is not None and edge_attr.numel() != E:
+        K = attr_width(edge_attr)
+        if edge_attr is not None and edge_attr.numel() != E * K:
             raise ValueError(
-                f"edge_attr must hold one value per edge (edge_dim=1): got shape "
-                f"{tuple(edge_attr.shape)} for {E} edges")
+                f"edge_attr must hold one value per edge (edge_dim=1) or be [E, edge_dim]: "
+                f"got shape {tuple(edge_attr.shape)} for {E} edges")
+        if K > _lib.MP_MAX_EDGE_DIM:
+            raise NotImplementedError(
+                f"edge_dim={K}: at most {_lib.MP_MAX_EDGE_DIM} edge attributes are implemented")
+        wide = edge_attr is not None and (K > 1 or with_eid)
+        self.edge_dim = K
         # PyG target_to_source: i = edge_index[0], j = edge_index[1] (flipped here)
         ei, attr = _canonical(edge_index, edge_attr, flow)
         dev = ei.device
@@ -128,17 +141,29 @@ class GineGraph:
         self.in_src = torch.empty(max(E, 1), **i32)
         self.out_dst = torch.empty(max(E, 1), **i32)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.in_attr = torch.empty(max(E, 1), **f32) if attr is not None else None
-        self.out_attr = torch.empty(max(E, 1), **f32) if attr is not None else None
+        shape = (max(E, 1), K) if K > 1 else (max(E, 1),)
+        self.in_attr = torch.empty(shape, **f32) if attr is not None else None
+        self.out_attr = torch.empty(shape, **f32) if attr is not None else None
+        self.out_eid = torch.empty(max(E, 1), **i32) if wide else None
         self._error = torch.zeros(1, **i32)
         ws_bytes = _lib.ctypes.c_size_t(0)
         _lib.call("gine_graph_workspace_bytes", self.num_nodes, E, _lib.ctypes.byref(ws_bytes))
         ws = torch.empty(max(int(ws_bytes.value), 1), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.call("gine_graph_build", _lib.ptr(ei), _lib.ptr(attr), self.num_nodes, E,
-                      _lib.ptr(self.in_rowptr), _lib.ptr(self.in_src), _lib.ptr(self.in_attr),
-                      _lib.ptr(self.out_rowptr), _lib.ptr(self.out_dst), _lib.ptr(self.out_attr),
-                      _lib.ptr(self._error), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev))
+            if wide:
+                _lib.call("gine_graph_build_ek", _lib.ptr(ei), _lib.ptr(attr), self.num_nodes,
+                          E, K, _lib.ptr(self.in_rowptr), _lib.ptr(self.in_src),
+                          _lib.ptr(self.in_attr), _lib.ptr(self.out_rowptr),
+                          _lib.ptr(self.out_dst), _lib.ptr(self.out_attr),
+                          _lib.ptr(self.out_eid), _lib.ptr(self._error), _lib.ptr(ws),
+                          ws.numel(), _lib.stream_handle(dev))
+            else:
+                _lib.call("gine_graph_build", _lib.ptr(ei), _lib.ptr(attr), self.num_nodes, E,
+                          _lib.ptr(self.in_rowptr), _lib.ptr(self.in_src),
+                          _lib.ptr(self.in_attr), _lib.ptr(self.out_rowptr),
+                          _lib.ptr(self.out_dst), _lib.ptr(self.out_attr),
+                          _lib.ptr(self._error), _lib.ptr(ws), ws.numel(),
+                          _lib.stream_handle(dev))
         # ws / ei / attr are freed on return: they were allocated on the current stream, so
         # the caching allocator only hands them out again to work ordered after the sort.
         self._checked = False
@@ -156,7 +181,7 @@ class GineGraph:
         kept when they fit its LDS with this graph's in-degree (gine_mp_fwd_layer_windows_fit):
         one small launch and one 8-byte readback per graph.  layer_windows = (tile windows
         [T, 2], largest window, largest in-edges of a tile)."""
-        if self.num_nodes <= 0 or self.in_attr is None:
+        if self.num_nodes <= 0 or self.in_attr is None or self.out_eid is not None:
             return
         tiles = (self.num_nodes + 31) // 32
         win = torch.empty(tiles, 2, dtype=torch.int32, device=self.device)
@@ -175,8 +200,8 @@ class GineGraph:
     def _plan_windows(self) -> None:
         mode, max_nodes = window_settings()
         self._windows = {"in": {}, "out": {}}
-        if mode == "off" or self.in_attr is None:
-            return
+        if mode == "off" or self.in_attr is None or self.out_eid is not None:
+            return  # (the window kernels carry one attribute per edge)
         # "all" forces the staged kernels wherever a plan exists (tests, experiments); "auto"
         # keeps only plans that stage a bounded multiple of the table
         staged = None if mode == "all" else WINDOW_MAX_STAGED
@@ -223,9 +248,17 @@ class GineGraph:
         return (self.out_rowptr[1:] - self.out_rowptr[:-1])
 
 
+def attr_width(edge_attr) -> int:
+    """edge_dim of an edge_attr tensor: K for [E, K] with K > 1, else 1 ([E], [E, 1])."""
+    if edge_attr is not None and edge_attr.dim() == 2 and edge_attr.size(1) > 1:
+        return int(edge_attr.size(1))
+    return 1
+
+
 def _canonical(edge_index, edge_attr, flow="source_to_target"):
     """(int64 [2, E] contiguous 16-byte-aligned edge list in source->target orientation,
-    fp32 [E] attributes or None) -- the form the graph build and the content check read."""
+    fp32 [E * edge_dim] attributes, row-major, or None) -- the form the graph build and the
+    content check read."""
     ei = edge_index.to(torch.int64)
     if flow == "target_to_source":
         ei = ei.flip(0)
@@ -285,19 +318,20 @@ class _GraphCache:
         self.stats = {"identity_hits": 0, "content_hits": 0, "builds": 0}
 
     @staticmethod
-    def _key(edge_index, edge_attr, num_nodes, flow):
+    def _key(edge_index, edge_attr, num_nodes, flow, with_eid=False):
         def tk(t):
             if t is None:
                 return None
             return (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype)
-        return (tk(edge_index), tk(edge_attr), int(num_nodes), flow, edge_index.device)
+        key = (tk(edge_index), tk(edge_attr), int(num_nodes), flow, edge_index.device)
+        return key + (True,) if with_eid else key
 
     def _remember(self, key, graph, edge_index, edge_attr):
         self._entries[key] = (graph, edge_index, edge_attr)
         while len(self._entries) > self.capacity:
             self._entries.popitem(last=False)
 
-    def _first_same(self, dev, ei, attr, cands) -> int:
+    def _first_same(self, dev, ei, attr, cands, edge_dim=1) -> int:
         """Index of the first candidate (graph, ref_ei, ref_attr) whose edge list (and
         attributes) equal ``ei`` / ``attr``, or -1: one device check per candidate into its
         own flag slot, then ONE synchronisation of the current stream."""
@@ -308,6 +342,11 @@ class _GraphCache:
         flag.host.zero_()
         stream = torch.cuda.current_stream(dev)
         for i, (_, ref_ei, ref_attr) in enumerate(cands):
+            if edge_dim > 1:  # all 4 * K * E attribute bytes
+                _lib.call("gine_graph_same_edges_ek", ref_ei.data_ptr(), ei.data_ptr(),
+                          _lib.ptr(ref_attr), _lib.ptr(attr), ei.size(1), edge_dim,
+                          flag.dev_ptr + 4 * i, stream.cuda_stream)
+                continue
             _lib.call("gine_graph_same_edges", ref_ei.data_ptr(), ei.data_ptr(),
                       _lib.ptr(ref_attr), _lib.ptr(attr), ei.size(1), flag.dev_ptr + 4 * i,
                       stream.cuda_stream)
@@ -319,8 +358,9 @@ class _GraphCache:
                 return i
         return -1
 
-    def get(self, edge_index, edge_attr, num_nodes, flow="source_to_target") -> GineGraph:
-        key = self._key(edge_index, edge_attr, num_nodes, flow)
+    def get(self, edge_index, edge_attr, num_nodes, flow="source_to_target",
+            with_eid=False) -> GineGraph:
+        key = self._key(edge_index, edge_attr, num_nodes, flow, with_eid)
         hit = self._entries.get(key)
         if hit is not None:
             self._entries.move_to_end(key)
@@ -330,13 +370,16 @@ class _GraphCache:
             self.stats["identity_hits"] += 1
             return graph
         capturing = torch.cuda.is_current_stream_capturing()
+        K = attr_width(edge_attr)
         ckey = (int(num_nodes), int(edge_index.size(-1)), flow, edge_index.device,
                 edge_attr is None)
+        if K > 1 or with_eid:  # (the K = 1 key is unchanged)
+            ckey = ckey + (K, bool(with_eid))
         cands = self._content.get(ckey) if not capturing and edge_index.is_cuda else None
         if cands:
             ei, attr = _canonical(edge_index, edge_attr, flow)
             usable = [c for c in cands if c[0]._checked]
-            i = self._first_same(edge_index.device, ei, attr, usable) if usable else -1
+            i = self._first_same(edge_index.device, ei, attr, usable, K) if usable else -1
             if i >= 0:
                 c = usable[i]
                 cands.remove(c)
@@ -345,7 +388,7 @@ class _GraphCache:
                 self._remember(key, c[0], edge_index, edge_attr)
                 self.stats["content_hits"] += 1
                 return c[0]
-        graph = GineGraph(edge_index, edge_attr, num_nodes, flow)
+        graph = GineGraph(edge_index, edge_attr, num_nodes, flow, with_eid)
         self.stats["builds"] += 1
         self._remember(key, graph, edge_index, edge_attr)
         if not capturing and edge_index.is_cuda:
@@ -368,5 +411,8 @@ class _GraphCache:
 graph_cache = _GraphCache()
 
 
-def get_graph(edge_index, edge_attr, num_nodes, flow="source_to_target") -> GineGraph:
-    return graph_cache.get(edge_index, edge_attr, num_nodes, flow)
+def get_graph(edge_index, edge_attr, num_nodes, flow="source_to_target",
+              with_eid: bool = False) -> GineGraph:
+    """``with_eid``: a K = 1 graph that also holds ``out_eid`` (GineGraph), for the gradient
+    with respect to ``edge_attr``; graphs with K > 1 always hold it."""
+    return graph_cache.get(edge_index, edge_attr, num_nodes, flow, with_eid)

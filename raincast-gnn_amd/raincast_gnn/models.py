@@ -25,7 +25,9 @@ class ResGnn(nn.Module):
     """models/gnn.py:10-45: a stack of GINEConv(Linear-BN-ReLU-Linear) with residuals."""
 
     def __init__(self, in_channels: int, out_channels: int, num_layers: int,
-                 hidden_channels: int):
+                 hidden_channels: int, edge_dim: int = 1):
+        """``edge_dim``: attributes per edge (the reference: 1, inverse distance); each layer's
+        ``lin`` is Linear(edge_dim, D) as PyG's GINEConv(edge_dim=...) makes it."""
         super().__init__()
         assert num_layers > 0, "num_layers must be > 0."
         self.convolutions = ModuleList()
@@ -34,7 +36,7 @@ class ResGnn(nn.Module):
             mlp = nn.Sequential(Linear(in_channels, hidden_channels),
                                 nn.BatchNorm1d(hidden_channels), ReLU(),
                                 Linear(hidden_channels, out))
-            self.convolutions.append(GINEConv(nn=mlp, train_eps=True, edge_dim=1))
+            self.convolutions.append(GINEConv(nn=mlp, train_eps=True, edge_dim=edge_dim))
             if layer == num_layers - 1:  # kept for parity; has no effect
                 out = out_channels
         self.relu = ReLU()
@@ -101,7 +103,7 @@ class GNN(nn.Module):
 
     def __init__(self, in_channels, hidden_channels_gnn, out_channels_gnn, num_layers_gnn,
                  optimizer_class=None, optimizer_params=None, loss="MixedLoss", grad_u=False,
-                 u=0.5, xi=0.5):
+                 u=0.5, xi=0.5, edge_dim=1):
         super().__init__()
         self.loss, self.grad_u, self.u, self.xi = loss, grad_u, u, xi
         self.loss_fn, self.out_channels = make_loss(loss, grad_u, u, xi)
@@ -110,7 +112,8 @@ class GNN(nn.Module):
                                       out_channels=hidden_channels_gnn)
         self.dim_red = RowLinear(in_channels + hidden_channels_gnn, hidden_channels_gnn)
         self.conv = ResGnn(in_channels=hidden_channels_gnn, hidden_channels=hidden_channels_gnn,
-                           out_channels=hidden_channels_gnn, num_layers=num_layers_gnn)
+                           out_channels=hidden_channels_gnn, num_layers=num_layers_gnn,
+                           edge_dim=edge_dim)
         self.aggr = RowLinear(out_channels_gnn, self.out_channels)
         self.postprocess = PostProcess(self.loss, self.grad_u)
         self.optimizer_class = optimizer_class
@@ -162,10 +165,12 @@ class GNN(nn.Module):
 
 
 def gnn_from_params(params: dict, in_channels: int = 35, **overrides) -> GNN:
-    """Build the model the way train.py:168-179 does from a params.json dict."""
+    """Build the model the way train.py:168-179 does from a params.json dict (plus an
+    optional "edge_dim" key, default 1)."""
     cfg = dict(params)
     cfg.update(overrides)
     return GNN(in_channels=in_channels, hidden_channels_gnn=cfg["gnn_hidden"],
                out_channels_gnn=cfg["gnn_hidden"], num_layers_gnn=cfg["gnn_layers"],
                optimizer_class=torch.optim.AdamW, optimizer_params={"lr": cfg["lr"]},
-               loss=cfg["loss"], grad_u=cfg["grad_u"], u=cfg["u"], xi=cfg["xi"])
+               loss=cfg["loss"], grad_u=cfg["grad_u"], u=cfg["u"], xi=cfg["xi"],
+               edge_dim=int(cfg.get("edge_dim", 1)))

@@ -11,6 +11,16 @@ state_dict keys (``nn.*``, ``eps``, ``lin.weight``, ``lin.bias``), ``reset_param
 and error behaviour.  ``forward`` runs the message passing in HIP and, when ``nn`` is
 ``Sequential(Linear(D,D), BatchNorm1d(D), ReLU(), Linear(D,D))`` with D in {32,64,128,256},
 the node MLP too; any other ``nn`` is applied to the HIP-aggregated features as a module.
+
+``edge_dim`` = 1 .. 8 (``edge_attr`` [E, edge_dim]; [E] too at 1): ``lin`` is
+``Linear(edge_dim, D)`` and the edge term is the chain ``e = b; e = fma(a[k], W[:, k], e)`` for
+k = 0 .. edge_dim - 1 (one rounding per term).  At ``edge_dim=1`` that is the reference
+configuration's path, unchanged.  ``edge_dim`` > 1, at up to 256 channels (a multiple of 4),
+runs the K-wide gather kernels (gine_mp_fwd_ek / gine_mp_bwd_ek): no window, fused or one-launch
+forms and no C++ binding there.  ``edge_attr.requires_grad`` is honoured at every supported
+``edge_dim`` (the backward then also writes d loss / d edge_attr; at ``edge_dim=1`` such a call
+runs the K-wide kernels as well).  Not implemented: ``edge_dim=None`` (edge features of width
+D), ``edge_dim`` > 8, ``edge_dim`` > 1 above 256 channels.
 """
 from __future__ import annotations
 
@@ -132,34 +142,53 @@ class GINEConv(torch.nn.Module):
                                  "Consider setting the 'edge_dim' attribute of 'GINEConv'")
             raise NotImplementedError("GINEConv without edge_dim (edge features of width D) "
                                       "is not implemented on the MI355X engine; use edge_dim=1")
-        if self.lin.in_features != 1:
-            raise NotImplementedError(f"edge_dim={self.lin.in_features}: only edge_dim=1 "
-                                      "(the reference configuration) is implemented")
+        K = self.lin.in_features
+        if K > _lib.MP_MAX_EDGE_DIM:
+            raise NotImplementedError(f"edge_dim={K}: at most edge_dim={_lib.MP_MAX_EDGE_DIM} "
+                                      "is implemented on the MI355X engine")
         if edge_attr is None:
             raise ValueError("GINEConv with edge_dim requires edge_attr")
-        if (edge_attr.dim() == 2 and edge_attr.size(1) != 1) or edge_attr.dim() > 2:
-            raise ValueError(f"edge_attr must be [E, 1] for edge_dim=1, got {tuple(edge_attr.shape)}")
-        if edge_attr.requires_grad:
-            raise NotImplementedError("gradients w.r.t. edge_attr are not implemented")
-        if self.lin.in_features == 1 and self.lin.out_features != x.size(1):
+        if K == 1:
+            if (edge_attr.dim() == 2 and edge_attr.size(1) != 1) or edge_attr.dim() > 2:
+                raise ValueError(
+                    f"edge_attr must be [E, 1] for edge_dim=1, got {tuple(edge_attr.shape)}")
+        elif edge_attr.dim() != 2 or edge_attr.size(1) != K:
+            raise ValueError(
+                f"edge_attr must be [E, {K}] for edge_dim={K}, got {tuple(edge_attr.shape)}")
+        if edge_attr.size(0) != edge_index.size(1):
+            raise ValueError(f"edge_attr holds {edge_attr.size(0)} rows for "
+                             f"{edge_index.size(1)} edges")
+        if self.lin.out_features != x.size(1):
             raise ValueError(f"lin projects to {self.lin.out_features} channels, x has {x.size(1)}")
+        if (K > 1 or edge_attr.requires_grad) and (x.size(1) % 4
+                                                   or x.size(1) > _lib.MP_EK_MAX_CHANNELS):
+            raise NotImplementedError(
+                f"edge_dim={K}{' with an edge_attr gradient' if K == 1 else ''} at {x.size(1)} "
+                f"channels: the K-wide message passing takes multiples of 4 up to "
+                f"{_lib.MP_EK_MAX_CHANNELS} channels")
         return x
 
     def _run(self, x, edge_index, edge_attr, size, epilogue, head=None):
         x = self._check_inputs(x, edge_index, edge_attr, size)
         edge_attr = edge_attr.float()
-        graph = get_graph(edge_index, edge_attr, x.size(0), self.flow)
+        # d loss / d edge_attr lands on this tensor; the graph reads a detached copy, built
+        # with out_eid (the K-wide kernels) when that gradient is wanted or edge_dim > 1
+        ea_grad = edge_attr if edge_attr.requires_grad and torch.is_grad_enabled() else None
+        graph = get_graph(edge_index, edge_attr.detach(), x.size(0), self.flow,
+                          with_eid=ea_grad is not None)
+        wide = graph.out_eid is not None
         if self._fusable(x):
             l1, bn, _, l2 = self.nn
-            ext = torch_ext.get() if USE_TORCH_EXT else None
+            ext = torch_ext.get() if USE_TORCH_EXT and not wide else None
             if ext is not None and gradbuf.slice_of(l1.weight) is None:
                 # the drop-in path (no flat gradient buffer: the non-deferred backward) from
                 # the C++ autograd binding -- the same launches, far less host time
                 return torch_ext.layer(ext, x, self, graph, epilogue)
             return GineLayer.apply(x, self.lin.weight, self.lin.bias, self.eps, l1.weight,
                                    l1.bias, bn.weight, bn.bias, l2.weight, l2.bias, graph,
-                                   BnConfig(bn), epilogue, head)
-        z = GineMessagePassing.apply(x, self.lin.weight, self.lin.bias, self.eps, graph)
+                                   BnConfig(bn), epilogue, head, ea_grad)
+        z = GineMessagePassing.apply(x, self.lin.weight, self.lin.bias, self.eps, graph,
+                                     ea_grad)
         out = self.nn(z)
         if epilogue == EPI_RELU:
             out = torch.relu(out)
