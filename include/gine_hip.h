@@ -47,7 +47,10 @@ extern "C" {
                                   gine_forecast_prob / _quantile / _score(_partials),
                                   gine_graph_build_ek / gine_graph_same_edges_ek and
                                   gine_mp_fwd_ek / gine_mp_bwd_ek(_num_partials, _finalize): edge_dim
-                                  up to GINE_MP_MAX_EDGE_DIM and the edge_attr gradient */
+                                  up to GINE_MP_MAX_EDGE_DIM and the edge_attr gradient,
+                                  gine_grad_sumsq(_num_partials) / gine_adamw_step_ctl /
+                                  gine_adamw_ctl_bytes: the AdamW step under a device control
+                                  block (schedule, clipping, skipping of non-finite steps) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -602,6 +605,73 @@ int gine_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_
                     float weight_decay, void* stream);
 /* Length in floats of gine_adamw_step's `step` buffer (288 since ABI 2). */
 int gine_adamw_state_floats(int64_t* floats);
+
+/* ------------------------------------------------------------------------------------
+ * The AdamW step under a device control block: learning-rate schedule, clipping by the
+ * global gradient norm (torch.nn.utils.clip_grad_norm_) and skipping of a step whose
+ * gradient is not finite.  Every decision is taken on the device from device-resident words,
+ * so a captured step follows a changed rate, bound or schedule on its next replay.
+ *
+ * gine_adamw_ctl (device memory, 4-byte fields, read by every launch, never written):
+ *   lr             base learning rate
+ *   max_norm       clipping bound; <= 0 or +inf: no clipping (the coefficient is exactly 1)
+ *   schedule       GINE_LR_CONSTANT, GINE_LR_COSINE or GINE_LR_LINEAR (both with warm-up)
+ *   warmup_steps   W, total_steps T, min_lr_ratio r.  With t = step count + 1 (1-based), in
+ *                  double, rounded once to float:
+ *                    constant            lr_t = lr
+ *                    t <= W              lr_t = lr * t / W
+ *                    otherwise, s = min(1, (t - W) / max(1, T - W)):
+ *                    cosine              lr_t = lr * (r + (1 - r) * 0.5 * (1 + cos(pi s)))
+ *                    linear              lr_t = lr * (r + (1 - r) * (1 - s))
+ *   skip_nonfinite non-zero: a step whose gradient holds an inf or a NaN (or whose norm
+ *                  overflows) writes nothing to param, exp_avg, exp_avg_sq or the step count
+ * gine_adamw_report (device memory, written by the launch's last workgroup beside its
+ * step-count store): lr_t, total_norm and clip_coef of the last launch; skipped = number of
+ * skipped steps, accumulated (the caller zeroes it once).
+ *
+ * gine_grad_sumsq: partials [num_partials][2] fp64, row b = {sum of g*g, number of
+ * non-finite g} over workgroup b's elements of grad [n] (16-byte aligned, like partials).
+ * One pass, fp64 accumulation in a fixed order that depends on n alone, plain stores: no
+ * atomics, no ticket, nothing to zero; the same input gives the same bits.  num_partials
+ * must be gine_grad_sumsq_num_partials(n) (a function of n only, at most 512; 0 for n = 0,
+ * when nothing is launched).
+ * gine_adamw_step_ctl: gine_adamw_step's update (same buffers, same `step` state and
+ * ticket, one launch) with lr_t from ctl and g' = g * clip_coef (one fp32 rounding; g' = g
+ * bit for bit when the coefficient is 1), where every workgroup sums the partials in index
+ * order in fp64, total_norm = (float)sqrt(sum) and
+ * clip_coef = min(1, max_norm / (total_norm + 1e-6f)) in fp32.  partials = NULL with
+ * num_partials = 0: no clipping and no non-finite test (total_norm reported as 0); then
+ * the step is this one launch.  Otherwise gine_grad_sumsq of the same grad and n must
+ * precede it on the stream.  ctl and report 4-byte aligned.
+ * gine_adamw_ctl_bytes: sizeof the two structs, for callers that allocate them as bytes.
+ * ---------------------------------------------------------------------------------- */
+#define GINE_LR_CONSTANT 0
+#define GINE_LR_COSINE 1
+#define GINE_LR_LINEAR 2
+typedef struct gine_adamw_ctl {
+  float lr;
+  float max_norm;
+  int32_t schedule;
+  float warmup_steps;
+  float total_steps;
+  float min_lr_ratio;
+  int32_t skip_nonfinite;
+} gine_adamw_ctl;
+typedef struct gine_adamw_report {
+  float lr_t;
+  float total_norm;
+  float clip_coef;
+  uint32_t skipped;
+} gine_adamw_report;
+int gine_grad_sumsq_num_partials(int64_t n, int32_t* num_partials);
+int gine_grad_sumsq(const float* grad, int64_t n, double* partials, int32_t num_partials,
+                    void* stream);
+int gine_adamw_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                        float* step, int64_t n, const gine_adamw_ctl* ctl,
+                        const double* partials, int32_t num_partials,
+                        gine_adamw_report* report, float beta1, float beta2, float eps,
+                        float weight_decay, void* stream);
+int gine_adamw_ctl_bytes(int64_t* ctl_bytes, int64_t* report_bytes);
 
 /* ------------------------------------------------------------------------------------
  * Fused CRPS losses (models/loss.py) over the post-processed predictions pred [N, K]

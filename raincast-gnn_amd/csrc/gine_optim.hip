@@ -127,3 +127,230 @@ extern "C" int gine_adamw_state_floats(int64_t* floats) {
   *floats = kAdamStateFloats;
   return GINE_OK;
 }
+
+// ---------------------------------------------------------------------------------------
+// The step under a device control block: learning-rate schedule, gradient clipping by the
+// global norm and skipping of a step whose gradient is not finite, all decided on the device
+// so that a captured step follows them on every replay.
+//   gine_grad_sumsq      one pass over the gradient: per workgroup {sum g*g, #non-finite g}
+//                        in fp64, fixed order, plain stores (no atomics, no ticket)
+//   gine_adamw_step_ctl  every workgroup sums the partials in index order, forms the clip
+//                        coefficient and this step's rate, then runs k_adamw's update
+// The launch boundary between the two is the only synchronisation.
+// ---------------------------------------------------------------------------------------
+namespace gine {
+namespace {
+
+constexpr int kAdamMaxBlocks = 512;  // the step's grid cap, shared by the norm's grid
+
+inline int64_t adam_blocks(int64_t n) {
+  int64_t blocks = ceil_div(n > 0 ? ceil_div(n, 4) : 1, 256);
+  return blocks > kAdamMaxBlocks ? kAdamMaxBlocks : blocks;
+}
+
+// Thread order: float4 i = tid, tid + stride, ... (x, y, z, w in turn), then the n % 4 tail
+// element of the grid's first threads; lanes by butterfly (every lane ends with the same
+// sum), the four waves in order through LDS.
+__global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g, int64_t n,
+                                                    double2* __restrict__ partials) {
+  __shared__ double s_sum[4];
+  __shared__ uint32_t s_bad[4];
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  double acc = 0.0;
+  uint32_t bad = 0;
+  auto take = [&](float v) {
+    acc += (double)v * (double)v;
+    bad += !(fabsf(v) < __builtin_inff());  // inf or NaN
+  };
+  for (int64_t i = tid; i < n4; i += stride) {
+    const float4 gi = reinterpret_cast<const float4*>(g)[i];
+    take(gi.x);
+    take(gi.y);
+    take(gi.z);
+    take(gi.w);
+  }
+  if (tid < n - 4 * n4) take(g[4 * n4 + tid]);
+  for (int off = 32; off > 0; off >>= 1) {
+    acc += shfl_xor_d(acc, off);
+    bad += __shfl_xor(bad, off, kWave);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_sum[threadIdx.x >> 6] = acc;
+    s_bad[threadIdx.x >> 6] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sum = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+    const uint32_t cnt = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3];
+    partials[blockIdx.x] = make_double2(sum, (double)cnt);
+  }
+}
+
+// lr_t of step t (1-based), in double, rounded once to float by the caller.
+__device__ __forceinline__ double scheduled_lr(const gine_adamw_ctl& c, double t) {
+  const double lr = (double)c.lr;
+  if (c.schedule != GINE_LR_COSINE && c.schedule != GINE_LR_LINEAR) return lr;
+  const double W = (double)c.warmup_steps, T = (double)c.total_steps;
+  if (t <= W) return lr * t / W;
+  const double s = fmin(1.0, (t - W) / fmax(1.0, T - W));
+  const double r = (double)c.min_lr_ratio;
+  if (c.schedule == GINE_LR_COSINE) return lr * (r + (1.0 - r) * 0.5 * (1.0 + cospi(s)));
+  return lr * (r + (1.0 - r) * (1.0 - s));
+}
+
+__global__ __launch_bounds__(256) void k_adamw_ctl(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, float* __restrict__ step, int64_t n,
+    const gine_adamw_ctl* __restrict__ ctl, const double2* __restrict__ partials,
+    int num_partials, gine_adamw_report* __restrict__ report, float beta1, float beta2,
+    float eps, float weight_decay) {
+  __shared__ double s_sum[kAdamMaxBlocks];
+  const gine_adamw_ctl c = *ctl;
+  const float t_new = step[0] + 1.0f;
+  const double t = (double)t_new;
+  const float lr = (float)scheduled_lr(c, t);
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  // the first trip's loads are issued before the norm is summed, which hides under them
+  int64_t i = tid;
+  float4 gi = f4_zero(), pi = f4_zero(), mi = f4_zero(), vi = f4_zero();
+  if (i < n4) {
+    gi = reinterpret_cast<const float4*>(g)[i];
+    pi = reinterpret_cast<float4*>(p)[i];
+    mi = reinterpret_cast<float4*>(m)[i];
+    vi = reinterpret_cast<float4*>(v)[i];
+  }
+  // the norm of the whole gradient: the same index-order sum in every workgroup, from LDS
+  // (one parallel round of global loads; a loop over global memory pays a round trip each).
+  // The non-finite counts are only tested against 0: an OR over the workgroup's threads.
+  double sumsq = 0.0;
+  bool bad = false;
+  if (num_partials > 0) {
+    bool mine = false;
+    for (int j = threadIdx.x; j < num_partials; j += blockDim.x) {
+      const double2 q = partials[j];
+      s_sum[j] = q.x;
+      mine |= q.y > 0.0;
+    }
+    bad = __syncthreads_or(mine) != 0;
+#pragma unroll 16
+    for (int j = 0; j < num_partials; ++j) sumsq += s_sum[j];
+  }
+  const float total_norm = (float)sqrt(sumsq);
+  float coef = 1.0f;
+  if (num_partials > 0 && c.max_norm > 0.0f && c.max_norm < __builtin_inff()) {
+    const float q = c.max_norm / (total_norm + 1e-6f);
+    coef = q > 1.0f ? 1.0f : q;  // clamp(max=1): a NaN stays a NaN
+  }
+  const bool skip = c.skip_nonfinite != 0 && num_partials > 0 &&
+                    (bad || !(total_norm < __builtin_inff()));
+  if (!skip) {
+    const AdamW op{(float)(1.0 - (double)lr * (double)weight_decay),
+                   (float)(-((double)lr / (1.0 - pow((double)beta1, t)))),
+                   (float)sqrt(1.0 - pow((double)beta2, t)), 1.0f - beta1, 1.0f - beta2, beta2,
+                   eps};
+    while (i < n4) {
+      op(gi.x * coef, pi.x, mi.x, vi.x);  // g * coef: one rounding (-ffp-contract=off)
+      op(gi.y * coef, pi.y, mi.y, vi.y);
+      op(gi.z * coef, pi.z, mi.z, vi.z);
+      op(gi.w * coef, pi.w, mi.w, vi.w);
+      reinterpret_cast<float4*>(p)[i] = pi;
+      reinterpret_cast<float4*>(m)[i] = mi;
+      reinterpret_cast<float4*>(v)[i] = vi;
+      i += stride;
+      if (i < n4) {
+        gi = reinterpret_cast<const float4*>(g)[i];
+        pi = reinterpret_cast<float4*>(p)[i];
+        mi = reinterpret_cast<float4*>(m)[i];
+        vi = reinterpret_cast<float4*>(v)[i];
+      }
+    }
+    if (tid < n - 4 * n4) {
+      const int64_t k = 4 * n4 + tid;
+      float pk = p[k], mk = m[k], vk = v[k];
+      op(g[k] * coef, pk, mk, vk);
+      p[k] = pk;
+      m[k] = mk;
+      v[k] = vk;
+    }
+  }
+  __syncthreads();  // every thread of this workgroup has read step[0]
+  if (threadIdx.x == 0) {
+    // k_adamw's two-level ticket; the top winner also writes the report
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(&step[1]);
+    const unsigned int grp = blockIdx.x % kAdamGroups;
+    const unsigned int groups = min(gridDim.x, (unsigned)kAdamGroups);
+    const unsigned int size = (gridDim.x - grp + kAdamGroups - 1) / kAdamGroups;
+    unsigned int* sub = reinterpret_cast<unsigned int*>(step + kAdamSubBase) + 32 * grp;
+    if (atomicAdd(sub, 1u) == size - 1) {
+      *sub = 0u;
+      if (atomicAdd(ticket, 1u) == groups - 1) {
+        if (!skip) step[0] = t_new;
+        report->lr_t = lr;
+        report->total_norm = total_norm;
+        report->clip_coef = coef;
+        if (skip) report->skipped = report->skipped + 1u;
+        *ticket = 0u;
+      }
+    }
+  }
+}
+
+}  // namespace
+}  // namespace gine
+
+extern "C" int gine_grad_sumsq_num_partials(int64_t n, int32_t* num_partials) {
+  if (n < 0 || !num_partials) return GINE_ERR_INVALID;
+  *num_partials = n > 0 ? (int32_t)adam_blocks(n) : 0;
+  return GINE_OK;
+}
+
+extern "C" int gine_grad_sumsq(const float* grad, int64_t n, double* partials,
+                               int32_t num_partials, void* stream) {
+  if (n < 0) return GINE_ERR_INVALID;
+  const int32_t want = n > 0 ? (int32_t)adam_blocks(n) : 0;
+  if (num_partials != want) return GINE_ERR_INVALID;
+  if (n == 0) return GINE_OK;
+  if (!grad || !partials) return GINE_ERR_INVALID;
+  if (((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(partials)) & 15) != 0)
+    return GINE_ERR_INVALID;
+  hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)want), dim3(256), 0, as_stream(stream), grad,
+                     n, reinterpret_cast<double2*>(partials));
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+extern "C" int gine_adamw_step_ctl(float* param, const float* grad, float* exp_avg,
+                                   float* exp_avg_sq, float* step, int64_t n,
+                                   const gine_adamw_ctl* ctl, const double* partials,
+                                   int32_t num_partials, gine_adamw_report* report, float beta1,
+                                   float beta2, float eps, float weight_decay, void* stream) {
+  if (n < 0 || !step || !ctl || !report) return GINE_ERR_INVALID;
+  if (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)) return GINE_ERR_INVALID;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+                       reinterpret_cast<uintptr_t>(exp_avg) |
+                       reinterpret_cast<uintptr_t>(exp_avg_sq) |
+                       reinterpret_cast<uintptr_t>(partials);
+  if (n > 0 && (al & 15) != 0) return GINE_ERR_INVALID;
+  if (((reinterpret_cast<uintptr_t>(ctl) | reinterpret_cast<uintptr_t>(report)) & 3) != 0)
+    return GINE_ERR_INVALID;
+  // NULL partials: no clipping and no non-finite test; otherwise gine_grad_sumsq's count
+  const int32_t want = (partials && n > 0) ? (int32_t)adam_blocks(n) : 0;
+  if (num_partials != want || (partials && n == 0)) return GINE_ERR_INVALID;
+  hipLaunchKernelGGL(k_adamw_ctl, dim3((unsigned)adam_blocks(n)), dim3(256), 0,
+                     as_stream(stream), param, grad, exp_avg, exp_avg_sq, step, n, ctl,
+                     reinterpret_cast<const double2*>(partials), (int)num_partials, report,
+                     beta1, beta2, eps, weight_decay);
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+extern "C" int gine_adamw_ctl_bytes(int64_t* ctl_bytes, int64_t* report_bytes) {
+  if (!ctl_bytes || !report_bytes) return GINE_ERR_INVALID;
+  *ctl_bytes = (int64_t)sizeof(gine_adamw_ctl);
+  *report_bytes = (int64_t)sizeof(gine_adamw_report);
+  return GINE_OK;
+}

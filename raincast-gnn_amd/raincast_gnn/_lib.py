@@ -61,6 +61,20 @@ class LayerHead(ctypes.Structure):
                 ("kind", _i32)]
 
 
+class AdamWCtl(ctypes.Structure):
+    """``gine_adamw_ctl`` (include/gine_hip.h): the device control block of
+    gine_adamw_step_ctl."""
+    _fields_ = [("lr", _f32), ("max_norm", _f32), ("schedule", _i32), ("warmup_steps", _f32),
+                ("total_steps", _f32), ("min_lr_ratio", _f32), ("skip_nonfinite", _i32)]
+
+
+class AdamWReport(ctypes.Structure):
+    """``gine_adamw_report`` (include/gine_hip.h)."""
+    _fields_ = [("lr_t", _f32), ("total_norm", _f32), ("clip_coef", _f32),
+                ("skipped", ctypes.c_uint32)]
+
+
+LR_CONSTANT, LR_COSINE, LR_LINEAR = 0, 1, 2  # GINE_LR_*
 GRAD_JOB_MP, GRAD_JOB_SLAB, GRAD_MAX_JOBS = 1, 2, 12
 MP_FUSED_MAX_DEGREE = 32  # GINE_MP_FUSED_MAX_DEGREE
 MP_MAX_EDGE_DIM = 8  # GINE_MP_MAX_EDGE_DIM
@@ -149,6 +163,11 @@ _SIGNATURES = {
     "gine_crps_bwd": [_c_void_p, _c_void_p, _c_void_p, _i64, _i32, _c_void_p, _c_void_p],
     "gine_count_valid": [_c_void_p, _i64, _c_void_p, _c_void_p],
     "gine_adamw_state_floats": [ctypes.POINTER(_i64)],
+    "gine_grad_sumsq_num_partials": [_i64, ctypes.POINTER(_i32)],
+    "gine_grad_sumsq": [_c_void_p, _i64, _c_void_p, _i32, _c_void_p],
+    "gine_adamw_step_ctl": [_c_void_p] * 5 + [_i64, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                              _f32, _f32, _f32, _f32, _c_void_p],
+    "gine_adamw_ctl_bytes": [ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "gine_crps_fwd_grad": [_c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _f64, _f64]
                           + [_c_void_p] * 8,
     "gine_crps_head_slab_floats": [_i64, _i32, _i32, ctypes.POINTER(ctypes.c_size_t)],

@@ -30,9 +30,38 @@ for _lt in ("24h", "72h", "120h"):
         EXPERIMENTS[f"{_lt}_{_name}"] = cfg
 
 
+_SCHEDULE_KEYS = {"kind", "warmup_steps", "total_steps", "min_lr_ratio"}
+_SCHEDULE_KINDS = ("constant", "cosine", "linear")
+
+
+def check_optimizer_keys(params: dict) -> None:
+    """The two optional keys this package adds to a ``params.json`` (none of the reference's
+    files has them): ``max_grad_norm`` (a positive number) and ``lr_schedule`` (``{"kind",
+    "warmup_steps", "total_steps", "min_lr_ratio"}``, only ``kind`` required;
+    ``total_steps`` defaults to ``max_epochs`` x the number of training batches)."""
+    if "max_grad_norm" in params:
+        v = params["max_grad_norm"]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
+            raise ValueError(f"params.json max_grad_norm={v!r}: expected a positive number")
+    if "lr_schedule" in params:
+        s = params["lr_schedule"]
+        if not isinstance(s, dict) or not set(s) <= _SCHEDULE_KEYS or "kind" not in s:
+            raise ValueError(f"params.json lr_schedule={s!r}: expected an object with 'kind' "
+                             f"and any of {sorted(_SCHEDULE_KEYS - {'kind'})}")
+        if s["kind"] not in _SCHEDULE_KINDS:
+            raise ValueError(f"params.json lr_schedule kind {s['kind']!r}: expected one of "
+                             f"{_SCHEDULE_KINDS}")
+        for k in ("warmup_steps", "total_steps", "min_lr_ratio"):
+            if k in s and (isinstance(s[k], bool) or not isinstance(s[k], (int, float))
+                           or s[k] < 0):
+                raise ValueError(f"params.json lr_schedule {k}={s[k]!r}: expected a number >= 0")
+
+
 def load_params(path: str) -> dict:
     with open(path) as f:
-        return json.load(f)
+        params = json.load(f)
+    check_optimizer_keys(params)
+    return params
 
 
 @dataclass(frozen=True)

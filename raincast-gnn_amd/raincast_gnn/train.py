@@ -97,6 +97,13 @@ class StepRunner:
     0.534 -> 0.548 ms per cfg2 step when split, DESIGN.md 5 -- the same choice and default
     as ``bench.py --allreduce``).  gloo groups always split (their collectives cannot be
     captured).
+
+    A default-mode FlatAdamW passes lr, betas, eps and weight_decay to its kernel by value, so
+    a capture freezes them: the runner remembers them per capture and, when they differ at
+    call time, drops that batch size's graphs and captures again after its warm-up.  A
+    control-mode FlatAdamW reads its rate from device memory and is never recaptured.  In
+    every form of the step ``opt.step()`` -- the norm launch included -- comes after the
+    all-reduce, so all ranks clip and skip alike.
     """
 
     def __init__(self, model, optimizer, graphed: bool = True, warmup: int = 2,
@@ -137,6 +144,14 @@ class StepRunner:
         self.opt.step()
         return loss.detach()
 
+    def _hyper(self):
+        """What a capture of ``opt.step()`` freezes: a default-mode FlatAdamW passes lr,
+        betas, eps and weight_decay by value (None for a control-mode one, whose rate is
+        read from device memory, and for torch optimizers)."""
+        if getattr(self.opt, "device_control", True):
+            return None
+        return self.opt.hyper()
+
     def __call__(self, batch: GraphBatch) -> torch.Tensor:
         """Run one step on ``batch``; returns the loss (a device scalar owned by the
         caller)."""
@@ -145,12 +160,17 @@ class StepRunner:
         if not self.graphed or dev.type != "cuda":
             return self.eager(batch)
         seen = self._seen.get(n, 0)
+        if n in self._graphs and self._graphs[n][4] != self._hyper():
+            # the optimizer's host scalars changed since the capture: drop this batch size's
+            # graphs and capture again after its warm-up
+            del self._graphs[n]
+            seen = 0
         self._seen[n] = seen + 1
         if seen < self.warmup:
             return self.eager(batch)
         if n not in self._graphs:
             self._capture(batch)
-        g_fb, g_opt, static, loss = self._graphs[n]
+        g_fb, g_opt, static, loss, _ = self._graphs[n]
         if static.edge_index is not batch.edge_index:
             return self.eager(batch)  # a different graph: not what was captured
         static.x.copy_(batch.x)
@@ -185,7 +205,7 @@ class StepRunner:
             g_opt = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_opt):
                 self.opt.step()
-        self._graphs[batch.num_graphs] = (g_fb, g_opt, static, loss)
+        self._graphs[batch.num_graphs] = (g_fb, g_opt, static, loss, self._hyper())
 
 
 def _mean_over_ranks(v: float, dev) -> float:
@@ -239,19 +259,63 @@ def sanity_forward(model, example: GraphBatch, device) -> torch.Tensor:
     return model(example.to(device))
 
 
+def opt_state_path(ckpt_path: str) -> str:
+    """``run_<id>-best.ckpt`` -> ``run_<id>-best.opt`` (FlatAdamW.state_dict of that epoch)."""
+    return os.path.splitext(ckpt_path)[0] + ".opt"
+
+
+def make_optimizer(parameters, config: dict, total_steps: int = 0):
+    """FlatAdamW from a ``params.json`` dict.  Without the optional ``max_grad_norm`` /
+    ``lr_schedule`` keys (the reference's files have neither) this is the plain
+    ``FlatAdamW(parameters, lr=config["lr"])``; with either, a control-mode optimizer whose
+    schedule's ``total_steps`` defaults to ``total_steps`` (max_epochs x batches per epoch)."""
+    from .optim import FlatAdamW, Schedule
+    from .params import check_optimizer_keys
+    check_optimizer_keys(config)
+    kw = {}
+    if config.get("max_grad_norm") is not None:
+        kw["max_grad_norm"] = float(config["max_grad_norm"])
+    if config.get("lr_schedule") is not None:
+        s = dict(config["lr_schedule"])
+        kw["schedule"] = Schedule(s["kind"], int(s.get("warmup_steps", 0)),
+                                  int(s.get("total_steps", total_steps)),
+                                  float(s.get("min_lr_ratio", 0.0)))
+    return FlatAdamW(parameters, lr=config["lr"], **kw)
+
+
+def load_resume(model, optimizer, ckpt_path: str, logger=None) -> None:
+    """Continue from a best checkpoint: the model's state_dict and, when the file beside it
+    exists, the optimizer's (copied into the existing flat buffers)."""
+    model.load_state_dict(torch.load(ckpt_path, map_location="cpu", weights_only=True))
+    path = opt_state_path(ckpt_path)
+    if os.path.exists(path):
+        optimizer.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+    (logger or log).info(f"Resumed from {ckpt_path}"
+                         + (f" and {path}" if os.path.exists(path) else " (no optimizer state)"))
+
+
 def fit(model, optimizer, train_loader, val_loader, device, max_epochs: int,
         ckpt_dir: str | None = None, run_id: str = "0", example: GraphBatch | None = None,
         logger=None, runner: StepRunner | None = None) -> dict:
     """train.py:179-208: sanity forward, then per epoch train + validate, saving the
-    state_dict whenever the validation loss improves.  Returns the loss history and the
-    best checkpoint."""
+    state_dict whenever the validation loss improves.  Returns the loss history (with the
+    number of optimizer steps skipped per epoch, and for a control-mode FlatAdamW each
+    epoch's last rate and gradient norm) and the best checkpoint; a FlatAdamW's state is
+    saved beside it as ``run_<id>-best.opt``."""
     logger = logger or log
     rank = dist.get_rank() if _world() > 1 else 0
     if example is not None:
         sanity_forward(model, example, device)
     runner = runner or StepRunner(model, optimizer)
     best, best_path = float("inf"), None
-    history = {"train": [], "val": []}
+    history = {"train": [], "val": [], "skipped": []}
+    # a control-mode FlatAdamW reports its rate, gradient norm and skipped steps from the
+    # device: one more small readback per epoch, after the loss readback
+    controlled = getattr(optimizer, "device_control", False)
+    flat = hasattr(optimizer, "views_intact")  # a FlatAdamW: its state is saved for --resume
+    if controlled:
+        history.update(lr=[], grad_norm=[])
+        skipped_before = optimizer.stats()["skipped_steps"]
     if ckpt_dir is not None:
         os.makedirs(ckpt_dir, exist_ok=True)
     logger.info(f"Starting training for {max_epochs} epochs...")
@@ -259,6 +323,16 @@ def fit(model, optimizer, train_loader, val_loader, device, max_epochs: int,
         logger.info(f"=== Epoch {epoch}/{max_epochs} ===")
         history["train"].append(train_one_epoch(model, train_loader, optimizer, device,
                                                 logger, runner))
+        skipped = 0
+        if controlled:
+            st = optimizer.stats()
+            skipped, skipped_before = st["skipped_steps"] - skipped_before, st["skipped_steps"]
+            history["lr"].append(st["lr"])
+            history["grad_norm"].append(st["grad_norm"])
+            norm = "n/a" if st["grad_norm"] is None else f"{st['grad_norm']:.4g}"
+            logger.info(f"  [Optim] lr: {st['lr']:.4g}, grad_norm: {norm}, "
+                        f"skipped steps: {skipped}")
+        history["skipped"].append(skipped)
         broadcast_buffers(model)
         val = evaluate(model, val_loader, device, logger)
         history["val"].append(val)
@@ -269,6 +343,8 @@ def fit(model, optimizer, train_loader, val_loader, device, max_epochs: int,
                 if rank == 0:
                     torch.save({k: v.detach().cpu().clone()
                                 for k, v in model.state_dict().items()}, best_path)
+                    if flat:  # beside it; the .ckpt stays a plain model state_dict
+                        torch.save(optimizer.state_dict(), opt_state_path(best_path))
                 logger.info(f"[Checkpoint] New best val_loss: {val:.6f}. Saved to {best_path}")
     logger.info("Training completed.")
     return {"history": history, "best_val_loss": best, "best_ckpt_path": best_path}
@@ -283,7 +359,6 @@ def main(argv=None) -> dict:
     from .distributed import (FlatGradReducer, broadcast_parameters, env_rank,
                               note_device_sharing)
     from .models import gnn_from_params
-    from .optim import FlatAdamW
     from .params import load_params
 
     ap = argparse.ArgumentParser(description="Train the station-graph GNN on the engine.")
@@ -301,6 +376,16 @@ def main(argv=None) -> dict:
     ap.add_argument("--allreduce", choices=("split", "graph"), default="split",
                     help="data-parallel all-reduce between the step's two graphs (split) or "
                          "captured inside one (graph, RCCL); see StepRunner")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the gradient to this global norm on the device (overrides "
+                         "params.json max_grad_norm)")
+    ap.add_argument("--schedule", choices=("constant", "cosine", "linear"), default=None,
+                    help="learning-rate schedule evaluated on the device (overrides "
+                         "params.json lr_schedule's kind)")
+    ap.add_argument("--warmup-steps", type=int, default=None,
+                    help="linear warm-up steps of --schedule cosine / linear")
+    ap.add_argument("--resume", metavar="PATH", default=None,
+                    help="a run_<id>-best.ckpt to continue from (with the .opt beside it)")
     args = ap.parse_args(argv)
 
     rank, local_rank, world = env_rank()
@@ -332,13 +417,25 @@ def main(argv=None) -> dict:
     val_loader = DeviceLoader(val_set, bs, shuffle=False)
     model = gnn_from_params(config, in_channels=samples[0].x.size(1)).to(device)
     broadcast_parameters(model)
-    opt = FlatAdamW(model.parameters(), lr=config["lr"])
+    epochs = args.epochs or config["max_epochs"]
+    if args.max_grad_norm is not None:
+        config["max_grad_norm"] = args.max_grad_norm
+    if args.schedule is not None or args.warmup_steps is not None:
+        sched = dict(config.get("lr_schedule") or {"kind": "constant"})
+        if args.schedule is not None:
+            sched["kind"] = args.schedule
+        if args.warmup_steps is not None:
+            sched["warmup_steps"] = args.warmup_steps
+        config["lr_schedule"] = sched
+    opt = make_optimizer(model.parameters(), config, total_steps=epochs * len(train_loader))
+    if args.resume:
+        load_resume(model, opt, args.resume, log)
     reducer = (FlatGradReducer(model.parameters(), flat=opt.flat_grad, offsets=opt._offsets)
                if world > 1 else None)
     runner = StepRunner(model, opt, graphed=not args.eager, reducer=reducer,
                         allreduce=args.allreduce)
-    out = fit(model, opt, train_loader, val_loader, device,
-              args.epochs or config["max_epochs"], os.path.join(args.dir, "models"),
+    out = fit(model, opt, train_loader, val_loader, device, epochs,
+              os.path.join(args.dir, "models"),
               args.run_id, example=train_set.batch(torch.tensor([0])), runner=runner)
     if world > 1:
         dist.destroy_process_group()
