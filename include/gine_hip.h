@@ -50,7 +50,9 @@ extern "C" {
                                   up to GINE_MP_MAX_EDGE_DIM and the edge_attr gradient,
                                   gine_grad_sumsq(_num_partials) / gine_adamw_step_ctl /
                                   gine_adamw_ctl_bytes: the AdamW step under a device control
-                                  block (schedule, clipping, skipping of non-finite steps) */
+                                  block (schedule, clipping, skipping of non-finite steps),
+                                  gine_ensemble_score / gine_ensemble_ecc: the raw ensemble's
+                                  scores and ECC members */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -772,6 +774,43 @@ int gine_forecast_score(const float* pred, const float* y, int64_t num_nodes, in
                         double u, double xi, double c, const double* x, int32_t num_x,
                         double* crps_rows, double* pit_lo, double* pit_hi, double* brier,
                         double* valid, double* partials, uint32_t* ticket, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The raw ensemble beside that distribution: M <= 64 members per row (one wavefront a row),
+ * read in place from a strided fp32 view: member i of row n is
+ *   x = shift + scale * (double)members[n * row_stride + i * member_stride]
+ * (strides in elements, >= 0; the affine undoes a StandardScaler column), all arithmetic and
+ * every result fp64.  A NaN member is missing: m = the row's number of valid members.  The
+ * stable rank of member i among the valid ones is
+ *   r_i = 1 + #{j valid : x_j < x_i or (x_j == x_i and j < i)}   (ties: lower index first).
+ * GINE_ERR_INVALID, before any HIP call, for num_members outside 1..64, a negative size or
+ * stride, a bad flag or a NULL operand.  num_rows = 0: GINE_OK, nothing launched.  One launch
+ * each, no workspace, no allocation, no host synchronisation (capturable); member sums in a
+ * fixed order (same bits every run).
+ * gine_ensemble_score: against targets y [N] fp32 (NaN = missing; y may be NULL), per row
+ *   crps      = (1/m) sum |x_i - y| - (1/(2 m^2)) sum_i sum_j |x_i - x_j|, the pair term formed
+ *               from the ranks as (1/m^2) sum_i (2 r_i - m - 1) x_i;
+ *   crps_fair = the same with 1/(2 m (m - 1)); NaN when m < 2;
+ *   rank_lo = #{x_i < y}, rank_hi = #{x_i <= y}: the observation's verification rank lies in
+ *               rank_lo..rank_hi of 0..m (the ensemble's pit_lo / pit_hi);
+ *   all four NaN for a NaN target or m = 0; members_valid = m (0 without members).
+ *   prob[n, t] = #{x_i > x[t]} / m for num_x device thresholds x (fp64): it does not read y,
+ *   NaN when m = 0.  Each row output may be NULL; num_x = 0 is allowed.
+ * gine_ensemble_ecc: ensemble copula coupling (ECC-Q): out[n, i] = the quantile of row n of
+ *   pred [N, K] (kind, u, xi, c as gine_forecast_quantile) at the level r_i / (m + 1), or
+ *   (r_i - 0.5) / m with GINE_ECC_MIDPOINT, formed by one division in double; NaN where member
+ *   i is missing.  out [N, num_members] fp64.
+ * ---------------------------------------------------------------------------------- */
+#define GINE_ECC_MIDPOINT 1
+int gine_ensemble_score(const float* members, int64_t row_stride, int64_t member_stride,
+                        int32_t num_members, double scale, double shift, const float* y,
+                        int64_t num_rows, const double* x, int32_t num_x, double* crps_rows,
+                        double* crps_fair_rows, double* rank_lo, double* rank_hi,
+                        double* members_valid, double* prob, void* stream);
+int gine_ensemble_ecc(const float* pred, int64_t num_nodes, int32_t kind, double u, double xi,
+                      double c, const float* members, int64_t row_stride, int64_t member_stride,
+                      int32_t num_members, double scale, double shift, int32_t flags,
+                      double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Weight/bias gradient of a plain Linear y = x W^T + b over many rows (the DeepSet,

@@ -335,6 +335,128 @@ __global__ __launch_bounds__(kThreads) void k_forecast_score(
   if (threadIdx.x == 0) *ticket = 0u;  // re-armed for the next call (stream order)
 }
 
+// ---------------------------------------------------------------------------------------
+// The raw ensemble beside the distribution.  One wave per row, lane i = member i (M <= 64),
+// four rows per workgroup; no LDS, no barrier, nothing shared between waves.  A member is
+// x = shift + scale * raw (two roundings, -ffp-contract=off), read in place through
+// (row_stride, member_stride); NaN = missing, and lanes >= M hold NaN too, so every
+// comparison below leaves them out by itself.  The stable rank among the valid members,
+//   r_i = 1 + #{j : x_j < x_i or (x_j == x_i and j < i)},
+// comes from M wave-uniform lane broadcasts (v_readlane_b32 pairs).  Sums over members are
+// butterflies over the 64 lanes: a fixed order, the same bits every run.
+// ---------------------------------------------------------------------------------------
+constexpr int kEnsRows = kThreads / kWave;  // rows per workgroup
+constexpr int kEnsMaxMembers = kWave;
+
+// lane j's value in every lane; j is wave-uniform
+__device__ __forceinline__ double lane_value(double v, int j) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), j);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
+  return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int off = kWave / 2; off > 0; off >>= 1) v += shfl_xor_d(v, off);
+  return v;
+}
+
+struct Member {
+  double x;  // this lane's member (NaN: missing or lane >= M)
+  int rank;  // 1..m among the valid ones (meaningless for a missing member)
+  int m;     // valid members of the row
+};
+
+__device__ __forceinline__ Member load_member(const float* __restrict__ members, int64_t row,
+                                              int64_t row_stride, int64_t member_stride, int M,
+                                              double scale, double shift) {
+  const int lane = threadIdx.x & (kWave - 1);
+  Member e;
+  e.x = __builtin_nan("");
+  if (lane < M) e.x = shift + scale * (double)members[row * row_stride + lane * member_stride];
+  e.m = __popcll(__ballot(e.x == e.x));
+  int r = 1;
+  for (int j = 0; j < M; ++j) {
+    const double xj = lane_value(e.x, j);
+    r += (xj < e.x || (xj == e.x && j < lane)) ? 1 : 0;
+  }
+  e.rank = r;
+  return e;
+}
+
+// Scores of the raw ensemble against y.  The pair term of the CRPS from the ranks:
+// sum_i sum_j |x_i - x_j| = 2 sum_i (2 r_i - m - 1) x_i (the sorted form; ties contribute 0
+// whichever of them takes which rank).
+__global__ __launch_bounds__(kThreads) void k_ensemble_score(
+    const float* __restrict__ members, int64_t row_stride, int64_t member_stride, int M,
+    double scale, double shift, const float* __restrict__ y, int64_t n,
+    const double* __restrict__ x, int T, double* __restrict__ crps,
+    double* __restrict__ crps_fair, double* __restrict__ rank_lo, double* __restrict__ rank_hi,
+    double* __restrict__ members_valid, double* __restrict__ prob) {
+  const int64_t row = blockIdx.x * (int64_t)kEnsRows + threadIdx.x / kWave;
+  if (row >= n) return;  // the whole wave
+  const int lane = threadIdx.x & (kWave - 1);
+  const double nan = __builtin_nan("");
+  const Member e = load_member(members, row, row_stride, member_stride, M, scale, shift);
+  const bool ok = e.x == e.x;
+  const double dm = (double)e.m;
+  // exceedance probabilities: lane k keeps threshold t0 + k's, one coalesced store per 64
+  for (int t0 = 0; t0 < T; t0 += kWave) {
+    const int cnt = min(kWave, T - t0);
+    double mine = nan;
+    for (int k = 0; k < cnt; ++k) {
+      const int above = __popcll(__ballot(e.x > x[t0 + k]));
+      if (lane == k) mine = (double)above / dm;  // 0 / 0 = NaN without members
+    }
+    if (lane < cnt) prob[row * (int64_t)T + t0 + lane] = mine;
+  }
+  const float yf = y ? y[row] : __builtin_nanf("");
+  double cr = nan, cf = nan, lo = nan, hi = nan;
+  if (yf == yf && e.m > 0) {  // wave-uniform
+    const double yy = (double)yf;
+    const double a = wave_sum(ok ? fabs(e.x - yy) : 0.0);
+    const double s = wave_sum(ok ? (double)(2 * e.rank - e.m - 1) * e.x : 0.0);
+    cr = a / dm - s / (dm * dm);
+    if (e.m > 1) cf = a / dm - s / (dm * (dm - 1.0));
+    lo = (double)__popcll(__ballot(e.x < yy));
+    hi = (double)__popcll(__ballot(e.x <= yy));
+  }
+  if (lane == 0) {
+    if (crps) crps[row] = cr;
+    if (crps_fair) crps_fair[row] = cf;
+    if (rank_lo) rank_lo[row] = lo;
+    if (rank_hi) rank_hi[row] = hi;
+    if (members_valid) members_valid[row] = dm;
+  }
+}
+
+// ECC-Q: member i becomes the predictive quantile at the level of its rank.
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_ensemble_ecc(
+    const float* __restrict__ pred, int64_t n, double u_fixed, double xi, double c,
+    const float* __restrict__ members, int64_t row_stride, int64_t member_stride, int M,
+    double scale, double shift, int midpoint, double* __restrict__ out) {
+  const int64_t row = blockIdx.x * (int64_t)kEnsRows + threadIdx.x / kWave;
+  if (row >= n) return;  // the whole wave
+  const int lane = threadIdx.x & (kWave - 1);
+  const Member e = load_member(members, row, row_stride, member_stride, M, scale, shift);
+  const RowP r = load_row<KIND>(pred, row, u_fixed, c);
+  // one division of exact operands: the IEEE value the host computes
+  const double level = midpoint ? ((double)e.rank - 0.5) / (double)e.m
+                                : (double)e.rank / (double)(e.m + 1);
+  double v = __builtin_nan("");
+  if (e.x == e.x) v = quantile_at<KIND>(r, level, false, c, xi);
+  if (lane < M) out[row * (int64_t)M + lane] = v;
+}
+
+// members view and sizes, before any HIP call
+int check_members(int64_t num_rows, int64_t row_stride, int64_t member_stride,
+                  int32_t num_members) {
+  if (num_rows < 0 || row_stride < 0 || member_stride < 0) return GINE_ERR_INVALID;
+  if (num_members < 1 || num_members > kEnsMaxMembers) return GINE_ERR_INVALID;
+  if (ceil_div(num_rows, kEnsRows) > 0x7fffffff) return GINE_ERR_TOO_LARGE;
+  return GINE_OK;
+}
+
 // kind, sizes and the distribution's domain (c < u, 0 < xi < 1), before any HIP call
 int check_domain(int64_t num_nodes, int32_t kind, double u, double xi, double c,
                  int64_t points) {
@@ -424,6 +546,56 @@ extern "C" int gine_forecast_score(const float* pred, const float* y, int64_t nu
     default: LAUNCH_SCORE(GINE_LOSS_MIXED_U); break;
   }
 #undef LAUNCH_SCORE
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+extern "C" int gine_ensemble_score(const float* members, int64_t row_stride,
+                                   int64_t member_stride, int32_t num_members, double scale,
+                                   double shift, const float* y, int64_t num_rows,
+                                   const double* x, int32_t num_x, double* crps_rows,
+                                   double* crps_fair_rows, double* rank_lo, double* rank_hi,
+                                   double* members_valid, double* prob, void* stream) {
+  const int rc = check_members(num_rows, row_stride, member_stride, num_members);
+  if (rc != GINE_OK) return rc;
+  if (num_x < 0) return GINE_ERR_INVALID;
+  if (num_x > kMaxPoints) return GINE_ERR_TOO_LARGE;
+  if (num_rows == 0) return GINE_OK;
+  if (!members) return GINE_ERR_INVALID;
+  if (num_x > 0 && (!x || !prob)) return GINE_ERR_INVALID;
+  const dim3 grid((unsigned)ceil_div(num_rows, kEnsRows));
+  hipLaunchKernelGGL(k_ensemble_score, grid, dim3(kThreads), 0, as_stream(stream), members,
+                     row_stride, member_stride, (int)num_members, scale, shift, y, num_rows, x,
+                     (int)num_x, crps_rows, crps_fair_rows, rank_lo, rank_hi, members_valid,
+                     prob);
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+extern "C" int gine_ensemble_ecc(const float* pred, int64_t num_nodes, int32_t kind, double u,
+                                 double xi, double c, const float* members, int64_t row_stride,
+                                 int64_t member_stride, int32_t num_members, double scale,
+                                 double shift, int32_t flags, double* out, void* stream) {
+  int rc = check_domain(num_nodes, kind, u, xi, c, 0);
+  if (rc != GINE_OK) return rc;
+  rc = check_members(num_nodes, row_stride, member_stride, num_members);
+  if (rc != GINE_OK) return rc;
+  if (flags & ~GINE_ECC_MIDPOINT) return GINE_ERR_INVALID;
+  if (num_nodes == 0) return GINE_OK;
+  if (!pred || !members || !out) return GINE_ERR_INVALID;
+  const dim3 grid((unsigned)ceil_div(num_nodes, kEnsRows));
+  const int midpoint = (flags & GINE_ECC_MIDPOINT) != 0;
+#define LAUNCH_ECC(KIND_)                                                                     \
+  hipLaunchKernelGGL((k_ensemble_ecc<KIND_>), grid, dim3(kThreads), 0, as_stream(stream),     \
+                     pred, num_nodes, u, xi, c, members, row_stride, member_stride,           \
+                     (int)num_members, scale, shift, midpoint, out)
+  switch (kind) {
+    case GINE_LOSS_NORMAL: LAUNCH_ECC(GINE_LOSS_NORMAL); break;
+    case GINE_LOSS_MIXED_NORMAL: LAUNCH_ECC(GINE_LOSS_MIXED_NORMAL); break;
+    case GINE_LOSS_MIXED: LAUNCH_ECC(GINE_LOSS_MIXED); break;
+    default: LAUNCH_ECC(GINE_LOSS_MIXED_U); break;
+  }
+#undef LAUNCH_ECC
   GINE_LAUNCH_STATUS();
   return GINE_OK;
 }

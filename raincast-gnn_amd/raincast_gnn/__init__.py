@@ -10,9 +10,10 @@ from .graph import GineGraph, get_graph, graph_cache
 from .nn import GINEConv
 from .inference import Predictor
 from .forecast import Forecast, ForecastScore, pit_sample
+from .ensemble import EnsembleScore, RawEnsemble, skill
 
-__all__ = ["Forecast", "ForecastScore", "GINEConv", "GineGraph", "Predictor", "get_graph",
-           "graph_cache", "native_library", "pit_sample"]
+__all__ = ["EnsembleScore", "Forecast", "ForecastScore", "GINEConv", "GineGraph", "Predictor",
+           "RawEnsemble", "get_graph", "graph_cache", "native_library", "pit_sample", "skill"]
 
 
 def native_library():

@@ -27,6 +27,8 @@ LOSS_NORMAL, LOSS_MIXED_NORMAL, LOSS_MIXED, LOSS_MIXED_U = 0, 1, 2, 3
 ABI_VERSION = 10
 COUNT_PARTS = 64  # GINE_COUNT_PARTS
 FORECAST_UPPER = 1  # GINE_FORECAST_UPPER
+ECC_MIDPOINT = 1  # GINE_ECC_MIDPOINT
+ENSEMBLE_MAX_MEMBERS = 64  # gine_ensemble_*: one wavefront per row
 
 _c_void_p = ctypes.c_void_p
 _i32, _i64, _f32, _size = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
@@ -181,6 +183,10 @@ _SIGNATURES = {
     "gine_forecast_score_partials": [_i64, _i32, ctypes.POINTER(_size)],
     "gine_forecast_score": [_c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i32]
                            + [_c_void_p] * 8,
+    "gine_ensemble_score": [_c_void_p, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64, _c_void_p,
+                            _i32] + [_c_void_p] * 7,
+    "gine_ensemble_ecc": [_c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i64, _i64, _i32,
+                          _f64, _f64, _i32, _c_void_p, _c_void_p],
     "gine_linear_wgrad_num_chunks": [_i64, _i32, _i32, ctypes.POINTER(_i32)],
     "gine_linear_wgrad": [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p,
                           _c_void_p, _f32, _c_void_p],

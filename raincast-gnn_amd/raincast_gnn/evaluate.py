@@ -9,6 +9,7 @@ Checkpoints load with ``torch.load(weights_only=True)``: a state_dict is plain t
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Iterable
 
 import torch
@@ -74,3 +75,35 @@ def verify(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor, t
     On a HIP device one launch; returns a :class:`raincast_gnn.forecast.ForecastScore`."""
     from .forecast import Forecast
     return Forecast.from_model(model, preds).score(targets, thresholds, unit=unit)
+
+
+@dataclass
+class EnsembleVerification:
+    """What :func:`verify_against_ensemble` returns; unpacks as ``(forecast, ensemble,
+    crpss)``.  The two mean CRPS values and ``crpss`` are over ``valid`` rows: those with a
+    target and at least one raw member (the rows both scores cover)."""
+    forecast: object
+    ensemble: object
+    crpss: torch.Tensor
+    model_crps: torch.Tensor
+    ensemble_crps: torch.Tensor
+    valid: torch.Tensor
+
+    def __iter__(self):
+        return iter((self.forecast, self.ensemble, self.crpss))
+
+
+def verify_against_ensemble(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor,
+                            raw, thresholds, unit: str = "mm") -> EnsembleVerification:
+    """:func:`verify` beside the raw ensemble's own scores (``raw``: a
+    :class:`raincast_gnn.ensemble.RawEnsemble` of the same rows) and the skill score
+    ``CRPSS = 1 - CRPS_model / CRPS_ensemble``, both means over the rows valid in both."""
+    from .ensemble import skill
+    fs = verify(model, preds, targets, thresholds, unit=unit)
+    es = raw.score(targets, thresholds, unit=unit)
+    both = ~torch.isnan(fs.crps_rows) & ~torch.isnan(es.crps_rows)
+    count = both.sum().double()
+    zero = torch.zeros_like(fs.crps_rows)
+    model_crps = torch.where(both, fs.crps_rows, zero).sum() / count
+    ens_crps = torch.where(both, es.crps_rows, zero).sum() / count
+    return EnsembleVerification(fs, es, skill(model_crps, ens_crps), model_crps, ens_crps, count)

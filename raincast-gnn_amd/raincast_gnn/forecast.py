@@ -204,6 +204,16 @@ class Forecast:
             return self._score_hip(y, x)
         return self._score_cpu(y, x)
 
+    def ecc(self, raw, levels: str = "uniform", unit: str = "model") -> torch.Tensor:
+        """Ensemble copula coupling (ECC-Q): the post-processed members ``[N, M]``.  Member
+        ``i`` of ``raw`` (a :class:`raincast_gnn.ensemble.RawEnsemble`) is replaced by this
+        distribution's quantile at the level of its stable rank ``r`` among the row's ``m``
+        valid members, ``r / (m + 1)`` (``"uniform"``) or ``(r - 0.5) / m`` (``"midpoint"``),
+        so the members keep the raw ensemble's rank structure across stations; NaN where the
+        raw member is NaN."""
+        from .ensemble import ecc
+        return self._to_unit(ecc(self, raw, levels), unit)
+
     # ------------------------------------------------------------------ HIP
     def _prob(self, x: torch.Tensor, upper: bool) -> torch.Tensor:
         if not self.pred.is_cuda:
@@ -281,7 +291,8 @@ class Forecast:
     def _quantile_cpu(self, level: torch.Tensor, upper: bool) -> torch.Tensor:
         r = self._rows()
         N = self.pred.size(0)
-        lv = level.reshape(1, -1).expand(N, -1)
+        # one level vector for all rows, or [N, Q]: each row's own levels (ECC)
+        lv = level if level.dim() == 2 else level.reshape(1, -1).expand(N, -1)
         inf = float("inf")
         s = lv if upper else 1.0 - lv
         v = s / r["q"]
