@@ -52,7 +52,10 @@ extern "C" {
                                   gine_adamw_ctl_bytes: the AdamW step under a device control
                                   block (schedule, clipping, skipping of non-finite steps),
                                   gine_ensemble_score / gine_ensemble_ecc: the raw ensemble's
-                                  scores and ECC members */
+                                  scores and ECC members,
+                                  gine_forecast_twcrps(_partials) / gine_ensemble_twcrps /
+                                  gine_crps_tw_fwd / _fwd_grad / _bwd: the threshold-weighted
+                                  CRPS as a score and as a loss term */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -811,6 +814,59 @@ int gine_ensemble_ecc(const float* pred, int64_t num_nodes, int32_t kind, double
                       double c, const float* members, int64_t row_stride, int64_t member_stride,
                       int32_t num_members, double scale, double shift, int32_t flags,
                       double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Threshold-weighted CRPS, weight 1{x >= t}, in model space, fp64 per row:
+ *   twCRPS_t(F, y) = int_t^inf (F(x) - 1{x >= y})^2 dx = CRPS(F_t, max(y, t)),
+ * F_t the distribution of max(Y, t).  With t' = max(t, c) for the three censored kinds
+ * (t' = t for GINE_LOSS_NORMAL) and y' = max(y, t'): the closed-form CRPS of the kind with
+ * c := t', y := y' (NORMAL: the MIXED_NORMAL form with p = 0); for MIXED / MIXED_U with
+ * t' >= u (the row's own u for MIXED_U) only the tail is left: with a = 1 - m_u,
+ * w(x) = 1 + xi (x - u) / sigma_u, e1 = -(1 - xi)/xi, e2 = -(2 - xi)/xi,
+ *   (y' - t') + 2 a sigma_u/(1 - xi) (w(y')^e1 - w(t')^e1) + a^2 sigma_u/(2 - xi) w(t')^e2.
+ * F is the where(y < u, ...) distribution of gine_forecast_score for MIXED_U too.
+ * gine_forecast_twcrps: pred / y / kind / u / xi / c as gine_forecast_score, x [num_x] device
+ *   thresholds (fp64).  rows [N, num_x] (may be NULL; NaN for a NaN target), mean [num_x] over
+ *   the valid rows (NaN when there is none), valid[0] their number (may be NULL).  A threshold
+ *   of -inf gives the row's CRPS at max(y, c) (at y for NORMAL), +inf gives 0, NaN gives NaN.
+ *   partials: gine_forecast_twcrps_partials doubles; ticket: one zeroed uint32, left at 0.
+ *   One launch, sums in a fixed order (same bits every run); num_x = 0 and num_nodes = 0
+ *   (nothing launched, nothing written) are allowed.
+ * gine_ensemble_twcrps: the arguments of gine_ensemble_score (y not NULL) and the crps /
+ *   crps_fair formulas of that entry applied to max(x_i, x[t]) and max(y, x[t]): rows and
+ *   fair_rows [N, num_x], NaN where gine_ensemble_score gives NaN and for a NaN threshold.
+ *   The members are ranked once per row (clamping is monotone).  There is no c here.
+ * gine_crps_tw_fwd / _fwd_grad / _bwd: gine_crps_fwd / _fwd_grad / _bwd for the per-node loss
+ *   (1 - tw_weight) * L_kind(pred, y) + tw_weight * twCRPS_{tw_threshold}(pred, y),
+ *   L_kind exactly the per-node loss of gine_crps_fwd (the sigmoid blend for MIXED_U), the tw
+ *   term differentiated through whichever branch the row takes, and through u for MIXED_U.
+ *   Both scalars are launch arguments (a captured step replays them); GINE_ERR_INVALID for
+ *   tw_weight outside [0, 1] or a non-finite tw_threshold.  Same partials
+ *   (gine_crps_num_partials), ticket, count_parts and outputs as the plain entries; dpred
+ *   holds the weighted sum, so _bwd only checks the two scalars.  There is no head-backward
+ *   form: the head backward of a tw loss is gine_head_bwd.
+ * ---------------------------------------------------------------------------------- */
+int gine_forecast_twcrps_partials(int64_t num_nodes, int32_t num_x, size_t* count);
+int gine_forecast_twcrps(const float* pred, const float* y, int64_t num_nodes, int32_t kind,
+                         double u, double xi, double c, const double* x, int32_t num_x,
+                         double* rows, double* mean, double* valid, double* partials,
+                         uint32_t* ticket, void* stream);
+int gine_ensemble_twcrps(const float* members, int64_t row_stride, int64_t member_stride,
+                         int32_t num_members, double scale, double shift, const float* y,
+                         int64_t num_rows, const double* x, int32_t num_x, double* rows,
+                         double* fair_rows, void* stream);
+int gine_crps_tw_fwd(const float* pred, const float* y, int64_t num_nodes, int32_t kind,
+                     double u, double xi, double c, double t, double tw_threshold,
+                     double tw_weight, double* dpred, double* partials, double* loss_out,
+                     double* count_out, uint32_t* ticket, void* stream);
+int gine_crps_tw_fwd_grad(const float* pred, const float* y, int64_t num_nodes, int32_t kind,
+                          double u, double xi, double c, double t, double tw_threshold,
+                          double tw_weight, double* dpred, double* partials, double* loss_out,
+                          double* count_out, uint32_t* ticket, const uint32_t* count_parts,
+                          float* grad_unit, void* stream);
+int gine_crps_tw_bwd(const double* dpred, const double* count, const double* gloss,
+                     int64_t num_nodes, int32_t kind, double tw_threshold, double tw_weight,
+                     float* grad_pred, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Weight/bias gradient of a plain Linear y = x W^T + b over many rows (the DeepSet,

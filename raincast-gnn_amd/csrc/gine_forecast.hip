@@ -448,6 +448,193 @@ __global__ __launch_bounds__(kThreads) void k_ensemble_ecc(
   if (lane < M) out[row * (int64_t)M + lane] = v;
 }
 
+// ---------------------------------------------------------------------------------------
+// Threshold-weighted CRPS, weight 1{x >= t}:
+//   twCRPS_t(F, y) = int_t^inf (F(x) - 1{x >= y})^2 dx = CRPS(F_t, max(y, t)),
+// F_t the distribution of max(Y, t).  With t' = max(t, c) (t itself for the uncensored
+// normal) and y' = max(y, t'), F_t is F censored at t': the closed forms above with c := t',
+// y := y' (twcrps_censored for the kinds without a tail).  Where t' has passed u only the
+// Pareto tail is left (twcrps_tail).
+// ---------------------------------------------------------------------------------------
+// t' >= u: a = 1 - m_u (omU: formed without cancellation), w(x) = 1 + xi (x - u) / sigma_u,
+//   (y' - t') + 2 a sigma_u/(1 - xi) (w(y')^e1 - w(t')^e1) + a^2 sigma_u/(2 - xi) w(t')^e2,
+// e1 = -(1 - xi)/xi, e2 = -(2 - xi)/xi; pareto_crps(y', u, m_u, sigma_u, xi) at t' = u.
+__device__ __forceinline__ double twcrps_tail(const RowP& r, double yp, double tp, double xi) {
+  const double wy = 1.0 + xi * ((yp - r.u) / r.su);
+  const double wt = 1.0 + xi * ((tp - r.u) / r.su);  // >= 1
+  const double e1 = -(1.0 - xi) / xi, e2 = -(2.0 - xi) / xi;
+  const double a = r.omU;
+  return (yp - tp) + ((2.0 / (1.0 - xi)) * (a * r.su * (pow(wy, e1) - pow(wt, e1))) +
+                      (1.0 / (2.0 - xi)) * (a * a * r.su * pow(wt, e2)));
+}
+
+// CRPS at y' >= t' of the normal with atom p censored at t': crps_mixed_normal(mu, sigma, p,
+// y', t') rewritten in upper probabilities S = q (1 - Phi),
+//   (y' - t') - 2 int_t'^y' S dx + int_t'^inf S^2 dx,
+//   int (1 - Phi) dz = z (1 - Phi) - phi,
+//   int_a^inf (1 - Phi)^2 dz = -a (1 - Phi(a))^2 + 2 phi(a) (1 - Phi(a)) - (1 - Phi(sqrt2 a))/sqrt(pi):
+// far up the tail the lower form subtracts terms of O(sigma z) from each other (1e-15 absolute
+// on values of 1e-5); here no term is larger than the result.
+__device__ __forceinline__ double twcrps_censored(double mu, double sigma, double p, double yp,
+                                                  double tp) {
+  const double yt = (yp - mu) / sigma;
+  const double ct = (tp - mu) / sigma;
+  const double q = 1.0 - p;
+  const double Uy = upper_phi(yt), Uc = upper_phi(ct);
+  const double G = (yt * Uy - phi(yt)) - (ct * Uc - phi(ct));
+  double H;
+  if (ct < 3.0) {
+    H = -(ct * (Uc * Uc)) + 2.0 * (phi(ct) * Uc) - kInvSqrtPi * upper_phi(kSqrt2 * ct);
+  } else {
+    // the same three terms with phi(z)^2 factored out, R = (1 - Phi) / phi the Mills ratio:
+    // they are 2 z^2 times their sum, and as products of exp() each also carries its argument
+    // rounding z^2 eps / 2 -- z^4 eps, 1e-10 of a value at z = 26; this way only the 2 z^2
+    const double kHalfPiSqrt = 1.25331413731550025121;  // sqrt(pi / 2)
+    const double R = kHalfPiSqrt * erfcx(ct / kSqrt2), R2 = kHalfPiSqrt * erfcx(ct);
+    const double f = phi(ct);
+    H = (f * f) * (2.0 * R - ct * (R * R) - kSqrt2 * R2);
+  }
+  return (yp - tp) + sigma * (q * (q * H - 2.0 * G));
+}
+
+template <int KIND>
+__device__ __forceinline__ double twcrps_row(const RowP& r, double y, double t, double c,
+                                             double xi) {
+  const double inf = __builtin_huge_val();
+  if (!(t == t)) return __builtin_nan("");  // fmax would drop the NaN
+  const double tp = Kind<KIND>::atom ? fmax(t, c) : t;
+  if (tp == inf) return 0.0;  // nothing above
+  const double yp = fmax(y, tp);
+  if constexpr (KIND == GINE_LOSS_NORMAL) {
+    if (tp == -inf) return crps_normal(r.mu, r.sigma, y);  // the censored form's limit
+    return twcrps_censored(r.mu, r.sigma, 0.0, yp, tp);
+  } else if constexpr (KIND == GINE_LOSS_MIXED_NORMAL) {
+    return twcrps_censored(r.mu, r.sigma, r.p, yp, tp);
+  } else {
+    if (tp < r.u) return crps_mixed(r.mu, r.sigma, r.p, r.su, r.u, yp, tp, xi);
+    return twcrps_tail(r, yp, tp, xi);
+  }
+}
+
+// k_forecast_score's layout: wave 0 loads the tile's rows into LDS, then the four waves take
+// the thresholds in turn (index T: the count of valid rows), lane = row; one butterfly sum per
+// threshold gives the workgroup's partial, the last ticket sums the partials in a fixed order.
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_forecast_twcrps(
+    const float* __restrict__ pred, const float* __restrict__ y, int64_t n, double u_fixed,
+    double xi, double c, const double* __restrict__ x, int T, double* __restrict__ rows_out,
+    double* __restrict__ mean, double* __restrict__ valid, double* __restrict__ partials,
+    unsigned int* __restrict__ ticket) {
+  __shared__ RowP s_row[kRows];
+  __shared__ double s_y[kRows];
+  __shared__ double s_red[kThreads];
+  __shared__ int s_last;
+  const double nan = __builtin_nan("");
+  const int64_t first = blockIdx.x * (int64_t)kRows;
+  const int rows = (int)min<int64_t>(kRows, n - first);
+  if (threadIdx.x < kRows) {
+    double ye = nan;
+    if ((int)threadIdx.x < rows) {
+      const int64_t i = first + threadIdx.x;
+      const float yf = y[i];
+      s_row[threadIdx.x] = load_row<KIND>(pred, i, u_fixed, c);
+      if (yf == yf) ye = (double)yf;
+    }
+    s_y[threadIdx.x] = ye;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & (kWave - 1);
+  const double ye = s_y[lane];
+  const bool ok = ye == ye;  // false for the lanes past the tile's rows too
+  double* part = partials + (size_t)blockIdx.x * (size_t)(T + 1);
+  for (int t = threadIdx.x / kWave; t <= T; t += kThreads / kWave) {
+    double v = ok ? 1.0 : 0.0;
+    if (t < T) {
+      const double r = ok ? twcrps_row<KIND>(s_row[lane], ye, x[t], c, xi) : nan;
+      if (rows_out && lane < rows) rows_out[(first + lane) * (int64_t)T + t] = r;
+      v = ok ? r : 0.0;
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) v += shfl_xor_d(v, off);
+    if (lane == 0)
+      __hip_atomic_exchange(&part[t], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();  // every wave's partials are out
+  if (threadIdx.x == 0) {
+    const unsigned int prev =
+        __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = prev == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // fixed order: thread j sums workgroups j, j + 256, ..., then one tree; the count first
+  const int P = gridDim.x;
+  double count = 0.0;
+  for (int k = 0; k <= T; ++k) {
+    const int t = k == 0 ? T : k - 1;
+    double a = 0.0;
+    for (int p = threadIdx.x; p < P; p += kThreads)
+      a += __hip_atomic_load(&partials[(size_t)p * (size_t)(T + 1) + t], __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+    s_red[threadIdx.x] = a;
+    __syncthreads();
+    for (int s = kThreads / 2; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) s_red[threadIdx.x] += s_red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      if (k == 0) {
+        count = s_red[0];
+        if (valid) valid[0] = count;
+      } else {
+        mean[t] = s_red[0] / count;  // NaN when no target is valid
+      }
+    }
+    __syncthreads();  // s_red[0] has been read
+  }
+  if (threadIdx.x == 0) *ticket = 0u;  // re-armed for the next call (stream order)
+}
+
+// The raw ensemble's twCRPS: crps / crps_fair of k_ensemble_score on max(x_i, t), max(y, t).
+// Clamping is monotone, so the members' stable ranks order the clamped values as well: one
+// ranking per row serves every threshold.  Lane k keeps threshold t0 + k's pair of values.
+__global__ __launch_bounds__(kThreads) void k_ensemble_twcrps(
+    const float* __restrict__ members, int64_t row_stride, int64_t member_stride, int M,
+    double scale, double shift, const float* __restrict__ y, int64_t n,
+    const double* __restrict__ x, int T, double* __restrict__ rows_out,
+    double* __restrict__ fair_out) {
+  const int64_t row = blockIdx.x * (int64_t)kEnsRows + threadIdx.x / kWave;
+  if (row >= n) return;  // the whole wave
+  const int lane = threadIdx.x & (kWave - 1);
+  const double nan = __builtin_nan("");
+  const Member e = load_member(members, row, row_stride, member_stride, M, scale, shift);
+  const bool ok = e.x == e.x;
+  const double dm = (double)e.m;
+  const double coef = (double)(2 * e.rank - e.m - 1);
+  const float yf = y[row];
+  const bool scored = yf == yf && e.m > 0;  // wave-uniform
+  const double yy = (double)yf;
+  for (int t0 = 0; t0 < T; t0 += kWave) {
+    const int cnt = min(kWave, T - t0);
+    double mine = nan, mine_fair = nan;
+    for (int k = 0; k < cnt; ++k) {
+      const double t = x[t0 + k];
+      if (!scored || !(t == t)) continue;  // wave-uniform
+      const double xc = fmax(e.x, t), yc = fmax(yy, t);
+      const double a = wave_sum(ok ? fabs(xc - yc) : 0.0);
+      const double s = wave_sum(ok ? coef * xc : 0.0);
+      if (lane == k) {
+        mine = a / dm - s / (dm * dm);
+        if (e.m > 1) mine_fair = a / dm - s / (dm * (dm - 1.0));
+      }
+    }
+    if (lane < cnt) {
+      rows_out[row * (int64_t)T + t0 + lane] = mine;
+      fair_out[row * (int64_t)T + t0 + lane] = mine_fair;
+    }
+  }
+}
+
 // members view and sizes, before any HIP call
 int check_members(int64_t num_rows, int64_t row_stride, int64_t member_stride,
                   int32_t num_members) {
@@ -596,6 +783,54 @@ extern "C" int gine_ensemble_ecc(const float* pred, int64_t num_nodes, int32_t k
     default: LAUNCH_ECC(GINE_LOSS_MIXED_U); break;
   }
 #undef LAUNCH_ECC
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+extern "C" int gine_forecast_twcrps_partials(int64_t num_nodes, int32_t num_x, size_t* count) {
+  return gine_forecast_score_partials(num_nodes, num_x, count);  // the same tiles and columns
+}
+
+extern "C" int gine_forecast_twcrps(const float* pred, const float* y, int64_t num_nodes,
+                                    int32_t kind, double u, double xi, double c, const double* x,
+                                    int32_t num_x, double* rows, double* mean, double* valid,
+                                    double* partials, uint32_t* ticket, void* stream) {
+  const int rc = check_domain(num_nodes, kind, u, xi, c, num_x);
+  if (rc != GINE_OK) return rc;
+  if (num_nodes == 0) return GINE_OK;
+  if (!pred || !y || !partials || !ticket) return GINE_ERR_INVALID;
+  if (num_x > 0 && (!x || !mean)) return GINE_ERR_INVALID;
+  const dim3 grid((unsigned)ceil_div(num_nodes, kRows));
+#define LAUNCH_TW(KIND_)                                                                       \
+  hipLaunchKernelGGL((k_forecast_twcrps<KIND_>), grid, dim3(kThreads), 0, as_stream(stream),   \
+                     pred, y, num_nodes, u, xi, c, x, (int)num_x, rows, mean, valid, partials, \
+                     ticket)
+  switch (kind) {
+    case GINE_LOSS_NORMAL: LAUNCH_TW(GINE_LOSS_NORMAL); break;
+    case GINE_LOSS_MIXED_NORMAL: LAUNCH_TW(GINE_LOSS_MIXED_NORMAL); break;
+    case GINE_LOSS_MIXED: LAUNCH_TW(GINE_LOSS_MIXED); break;
+    default: LAUNCH_TW(GINE_LOSS_MIXED_U); break;
+  }
+#undef LAUNCH_TW
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+extern "C" int gine_ensemble_twcrps(const float* members, int64_t row_stride,
+                                    int64_t member_stride, int32_t num_members, double scale,
+                                    double shift, const float* y, int64_t num_rows,
+                                    const double* x, int32_t num_x, double* rows,
+                                    double* fair_rows, void* stream) {
+  const int rc = check_members(num_rows, row_stride, member_stride, num_members);
+  if (rc != GINE_OK) return rc;
+  if (num_x < 0) return GINE_ERR_INVALID;
+  if (num_x > kMaxPoints) return GINE_ERR_TOO_LARGE;
+  if (num_rows == 0 || num_x == 0) return GINE_OK;
+  if (!members || !y || !x || !rows || !fair_rows) return GINE_ERR_INVALID;
+  const dim3 grid((unsigned)ceil_div(num_rows, kEnsRows));
+  hipLaunchKernelGGL(k_ensemble_twcrps, grid, dim3(kThreads), 0, as_stream(stream), members,
+                     row_stride, member_stride, (int)num_members, scale, shift, y, num_rows, x,
+                     (int)num_x, rows, fair_rows);
   GINE_LAUNCH_STATUS();
   return GINE_OK;
 }

@@ -9,11 +9,12 @@ from . import _lib
 from .graph import GineGraph, get_graph, graph_cache
 from .nn import GINEConv
 from .inference import Predictor
-from .forecast import Forecast, ForecastScore, pit_sample
-from .ensemble import EnsembleScore, RawEnsemble, skill
+from .forecast import Forecast, ForecastScore, TwScore, pit_sample
+from .ensemble import EnsembleScore, EnsembleTwScore, RawEnsemble, skill
 
-__all__ = ["EnsembleScore", "Forecast", "ForecastScore", "GINEConv", "GineGraph", "Predictor",
-           "RawEnsemble", "get_graph", "graph_cache", "native_library", "pit_sample", "skill"]
+__all__ = ["EnsembleScore", "EnsembleTwScore", "Forecast", "ForecastScore", "GINEConv",
+           "GineGraph", "Predictor", "RawEnsemble", "TwScore", "get_graph", "graph_cache",
+           "native_library", "pit_sample", "skill"]
 
 
 def native_library():

@@ -187,6 +187,15 @@ _SIGNATURES = {
                             _i32] + [_c_void_p] * 7,
     "gine_ensemble_ecc": [_c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i64, _i64, _i32,
                           _f64, _f64, _i32, _c_void_p, _c_void_p],
+    "gine_forecast_twcrps_partials": [_i64, _i32, ctypes.POINTER(_size)],
+    "gine_forecast_twcrps": [_c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i32]
+                            + [_c_void_p] * 6,
+    "gine_ensemble_twcrps": [_c_void_p, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64, _c_void_p,
+                             _i32] + [_c_void_p] * 3,
+    "gine_crps_tw_fwd": [_c_void_p, _c_void_p, _i64, _i32] + [_f64] * 6 + [_c_void_p] * 6,
+    "gine_crps_tw_fwd_grad": [_c_void_p, _c_void_p, _i64, _i32] + [_f64] * 6 + [_c_void_p] * 8,
+    "gine_crps_tw_bwd": [_c_void_p, _c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _c_void_p,
+                         _c_void_p],
     "gine_linear_wgrad_num_chunks": [_i64, _i32, _i32, ctypes.POINTER(_i32)],
     "gine_linear_wgrad": [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p,
                           _c_void_p, _f32, _c_void_p],

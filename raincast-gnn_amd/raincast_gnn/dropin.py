@@ -66,9 +66,10 @@ class ReferenceStructGNN(nn.Module):
     """models/gnn.py:70-141 with torch layers and the engine's GINEConv."""
 
     def __init__(self, in_channels, hidden_channels_gnn, out_channels_gnn, num_layers_gnn,
-                 loss="MixedLoss", grad_u=False, u=0.5, xi=0.5):
+                 loss="MixedLoss", grad_u=False, u=0.5, xi=0.5, tw_threshold=None,
+                 tw_weight=0.0):
         super().__init__()
-        self.loss_fn, self.out_channels = make_loss(loss, grad_u, u, xi)
+        self.loss_fn, self.out_channels = make_loss(loss, grad_u, u, xi, tw_threshold, tw_weight)
         self.loss_fn.fused = False   # the reference's torch loss, not the fused kernel
         self.deepset = DeepSetEncoder(in_channels, hidden_channels_gnn, hidden_channels_gnn)
         self.dim_red = nn.Linear(in_channels + hidden_channels_gnn, hidden_channels_gnn)
@@ -84,8 +85,14 @@ class ReferenceStructGNN(nn.Module):
         return self.postprocess(self.aggr(h))
 
 
+GNN = ReferenceStructGNN  # the name models.GNN's users expect here
+
+
 def reference_struct_from_params(params: dict, in_channels: int = 35) -> ReferenceStructGNN:
     """train.py:168-179's construction from a params.json dict."""
+    from .params import tw_from_params
+    tw_threshold, tw_weight = tw_from_params(params)
     return ReferenceStructGNN(in_channels, params["gnn_hidden"], params["gnn_hidden"],
                               params["gnn_layers"], loss=params["loss"],
-                              grad_u=params["grad_u"], u=params["u"], xi=params["xi"])
+                              grad_u=params["grad_u"], u=params["u"], xi=params["xi"],
+                              tw_threshold=tw_threshold, tw_weight=tw_weight)

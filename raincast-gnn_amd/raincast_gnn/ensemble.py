@@ -65,6 +65,20 @@ class EnsembleScore:
         return torch.nansum(self.crps_fair_rows) / (~torch.isnan(self.crps_fair_rows)).sum()
 
 
+@dataclass
+class EnsembleTwScore:
+    """Threshold-weighted CRPS of the raw ensemble: ``rows`` / ``fair_rows [N, T]`` (NaN where
+    :class:`EnsembleScore` has NaN), their means ``mean`` / ``mean_fair [T]`` over the rows that
+    have a value, ``valid`` the number of rows with a target and a member (a 1-element fp64
+    tensor) and the ``thresholds [T]`` in model space."""
+    rows: torch.Tensor
+    fair_rows: torch.Tensor
+    mean: torch.Tensor
+    mean_fair: torch.Tensor
+    valid: torch.Tensor
+    thresholds: torch.Tensor
+
+
 def skill(model_crps, ensemble_crps):
     """The CRPSS ``1 - model / ensemble``: positive where the model beats the ensemble."""
     return 1.0 - model_crps / ensemble_crps
@@ -137,6 +151,26 @@ class RawEnsemble:
         brier = torch.where(ok.unsqueeze(1), d * d, torch.zeros_like(d)).sum(0) / valid
         return EnsembleScore(crps, rows[1], rows[2], rows[3], rows[4], prob, brier, valid)
 
+    def twcrps(self, y: torch.Tensor, thresholds, unit: str = "model") -> EnsembleTwScore:
+        """Threshold-weighted CRPS of the targets ``y [N]`` at each threshold, weight
+        ``1{x >= t}``: the ``crps`` / ``crps_fair`` formulas on ``max(x_i, t)`` and ``max(y, t)``
+        (there is no censoring point here: the ensemble is whatever its members are).  Finite or
+        ``-inf`` thresholds; NaN for a NaN threshold."""
+        x = _thresholds(thresholds, unit, self.device)
+        y = y.detach().to(self.device).float().reshape(-1).contiguous()
+        N, T = self.members.size(0), x.numel()
+        if y.numel() != N:
+            raise ValueError(f"y must have {N} entries, got {y.numel()}")
+        rows, fair = self._twcrps_hip(y, x) if self.on_kernel else self._twcrps_torch(y, x)
+        ok = ~torch.isnan(y) & ((~torch.isnan(self.members)).sum(1) > 0)
+        valid = ok.sum().double().reshape(1)
+        mean = torch.where(ok.unsqueeze(1), rows, torch.zeros_like(rows)).sum(0) / valid
+        has = ~torch.isnan(fair)
+        mean_fair = torch.where(has, fair, torch.zeros_like(fair)).sum(0) / has.sum(0).double()
+        mean_fair = torch.where(torch.isnan(x), torch.full_like(mean_fair, float("nan")),
+                                mean_fair)
+        return EnsembleTwScore(rows, fair, mean, mean_fair, valid, x)
+
     def exceedance(self, thresholds, unit: str = "model") -> torch.Tensor:
         """``#{x_i > threshold} / m`` per row and threshold (NaN for a row without members)."""
         x = _thresholds(thresholds, unit, self.device)
@@ -170,6 +204,15 @@ class RawEnsemble:
     def _score_hip(self, y: torch.Tensor, x: torch.Tensor):
         rows = torch.empty(5, self.members.size(0), dtype=torch.float64, device=self.device)
         return rows, self._launch_score(y, x, rows)
+
+    def _twcrps_hip(self, y: torch.Tensor, x: torch.Tensor):
+        mem = self.members
+        N, T = mem.size(0), x.numel()
+        out = torch.empty(2, N, T, dtype=torch.float64, device=self.device)
+        _lib.call("gine_ensemble_twcrps", _lib.ptr(mem), mem.stride(0), mem.stride(1),
+                  mem.size(1), self.scale, self.shift, _lib.ptr(y), N, _lib.ptr(x), T,
+                  _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.stream_handle(self.device))
+        return out[0], out[1]
 
     # ------------------------------------------------------------------ torch (fp64)
     def _ranks(self):
@@ -205,6 +248,25 @@ class RawEnsemble:
         rows = torch.stack([torch.where(ok, crps, nan), torch.where(ok, fair, nan),
                             torch.where(ok, lo, nan), torch.where(ok, hi, nan), dm])
         return rows, prob
+
+    def _twcrps_torch(self, y: torch.Tensor, x: torch.Tensor):
+        v, xs, _, m = self._ranks()
+        N, M = v.shape
+        dm = m.double().unsqueeze(1)                                       # [N, 1]
+        t = x.reshape(1, 1, -1)
+        yc = torch.maximum(y.double().reshape(-1, 1, 1), t)                # [N, 1, T]
+        miss = torch.isnan(v).unsqueeze(2)
+        vc = torch.maximum(torch.nan_to_num(v).unsqueeze(2), t)           # [N, M, T]
+        a = torch.where(miss, torch.zeros_like(vc), (vc - yc).abs()).sum(1)
+        k = torch.arange(1, M + 1, device=v.device, dtype=torch.float64).reshape(1, -1, 1)
+        coef = 2.0 * k - dm.unsqueeze(2) - 1.0
+        xc = torch.maximum(torch.nan_to_num(xs).unsqueeze(2), t)          # sorted: NaN last
+        s = torch.where(torch.isnan(xs).unsqueeze(2), torch.zeros_like(xc), coef * xc).sum(1)
+        nan = torch.full_like(a, float("nan"))
+        ok = (~torch.isnan(y) & (m > 0)).unsqueeze(1) & ~torch.isnan(x).unsqueeze(0)
+        rows = torch.where(ok, a / dm - s / (dm * dm), nan)
+        fair = torch.where(ok & (m > 1).unsqueeze(1), a / dm - s / (dm * (dm - 1.0)), nan)
+        return rows, fair
 
     def _levels_torch(self, levels: str) -> torch.Tensor:
         """The ECC level of every member [N, M] (NaN where it is missing)."""

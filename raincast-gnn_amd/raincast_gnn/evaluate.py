@@ -107,3 +107,35 @@ def verify_against_ensemble(model: torch.nn.Module, preds: torch.Tensor, targets
     model_crps = torch.where(both, fs.crps_rows, zero).sum() / count
     ens_crps = torch.where(both, es.crps_rows, zero).sum() / count
     return EnsembleVerification(fs, es, skill(model_crps, ens_crps), model_crps, ens_crps, count)
+
+
+@dataclass
+class TwVerification:
+    """What :func:`verify_tw` returns, per threshold: the model's and the raw ensemble's mean
+    twCRPS over the ``valid`` rows (those with a value in both), and the skill
+    ``1 - model / ensemble``; ``thresholds`` in model space."""
+    model: torch.Tensor
+    ensemble: torch.Tensor
+    skill: torch.Tensor
+    valid: torch.Tensor
+    thresholds: torch.Tensor
+
+
+def verify_tw(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor, raw, thresholds,
+              unit: str = "mm") -> TwVerification:
+    """The threshold-weighted CRPS of the predictions beside the raw ensemble's (``raw``: a
+    :class:`raincast_gnn.ensemble.RawEnsemble` of the same rows) at each threshold (``unit``:
+    millimetres by default), and the skill ``1 - model / ensemble``: how much better than the
+    ensemble the model is above the threshold.  Means over the rows valid in both, as
+    :func:`verify_against_ensemble`."""
+    from .ensemble import skill
+    from .forecast import Forecast
+    ft = Forecast.from_model(model, preds).twcrps(targets, thresholds, unit=unit, rows=True)
+    et = raw.twcrps(targets.to(raw.device), thresholds, unit=unit)
+    er = et.rows.to(ft.rows.device)
+    both = ~torch.isnan(ft.rows) & ~torch.isnan(er)
+    count = both.sum(0).double()
+    zero = torch.zeros_like(ft.rows)
+    m = torch.where(both, ft.rows, zero).sum(0) / count
+    e = torch.where(both, er, zero).sum(0) / count
+    return TwVerification(m, e, skill(m, e), count, ft.thresholds)

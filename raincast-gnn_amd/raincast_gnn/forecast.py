@@ -78,6 +78,18 @@ class ForecastScore:
         return torch.nansum(self.crps_rows) / self.valid[0]
 
 
+@dataclass
+class TwScore:
+    """Threshold-weighted CRPS of a set of targets (:mod:`raincast_gnn.twcrps`): ``mean [T]``
+    over the ``valid`` rows (a 1-element fp64 tensor; NaN means when there is none), ``rows
+    [N, T]`` (NaN where the target is NaN) when asked for, and the ``thresholds [T]`` in model
+    space."""
+    mean: torch.Tensor
+    valid: torch.Tensor
+    rows: torch.Tensor | None
+    thresholds: torch.Tensor
+
+
 def pit_sample(lo: torch.Tensor, hi: torch.Tensor, generator=None) -> torch.Tensor:
     """The randomised PIT ``lo + U (hi - lo)``, ``U`` uniform on [0, 1): uniform under a
     calibrated forecast, atoms included (for a histogram).  NaN rows stay NaN."""
@@ -204,6 +216,19 @@ class Forecast:
             return self._score_hip(y, x)
         return self._score_cpu(y, x)
 
+    def twcrps(self, y: torch.Tensor, thresholds, unit: str = "model",
+               rows: bool = False) -> TwScore:
+        """Threshold-weighted CRPS of the targets ``y [N]`` (model space, NaN = missing) at each
+        threshold (``unit``: the thresholds'), weight ``1{x >= t}``: the part of the CRPS integral
+        above ``t`` (:mod:`raincast_gnn.twcrps`).  ``rows``: also the per-row values."""
+        x = self._thresholds(thresholds, unit)
+        y = y.detach().to(self.pred.device).float().reshape(-1).contiguous()
+        if y.numel() != self.pred.size(0):
+            raise ValueError(f"y must have {self.pred.size(0)} entries, got {y.numel()}")
+        if self.pred.is_cuda:
+            return self._twcrps_hip(y, x, rows)
+        return self._twcrps_cpu(y, x, rows)
+
     def ecc(self, raw, levels: str = "uniform", unit: str = "model") -> torch.Tensor:
         """Ensemble copula coupling (ECC-Q): the post-processed members ``[N, M]``.  Member
         ``i`` of ``raw`` (a :class:`raincast_gnn.ensemble.RawEnsemble`) is replaced by this
@@ -249,7 +274,32 @@ class Forecast:
                   _lib.ptr(_ticket(dev)), _lib.stream_handle(dev))
         return ForecastScore(rows[0], rows[1], rows[2], brier, valid)
 
+    def _twcrps_hip(self, y: torch.Tensor, x: torch.Tensor, rows: bool) -> TwScore:
+        dev = self.pred.device
+        N, T = self.pred.size(0), x.numel()
+        out = torch.empty(N, T, dtype=torch.float64, device=dev) if rows else None
+        mean = torch.full((T,), float("nan"), dtype=torch.float64, device=dev) if N == 0 \
+            else torch.empty(T, dtype=torch.float64, device=dev)
+        valid = torch.zeros(1, dtype=torch.float64, device=dev)
+        count = ctypes.c_size_t(0)
+        _lib.call("gine_forecast_twcrps_partials", N, T, ctypes.byref(count))
+        partials = torch.empty(count.value, dtype=torch.float64, device=dev)
+        _lib.call("gine_forecast_twcrps", _lib.ptr(self.pred), _lib.ptr(y), N, self.kind, self.u,
+                  self.xi, self.c, _lib.ptr(x), T, _lib.ptr(out), _lib.ptr(mean), _lib.ptr(valid),
+                  _lib.ptr(partials), _lib.ptr(_ticket(dev)), _lib.stream_handle(dev))
+        return TwScore(mean, valid, out, x)
+
     # ------------------------------------------------------------------ CPU (fp64 torch)
+    def _twcrps_cpu(self, y: torch.Tensor, x: torch.Tensor, rows: bool) -> TwScore:
+        from .twcrps import tw_rows_of
+        ok = ~torch.isnan(y)
+        y1 = torch.where(ok, y, torch.zeros_like(y)).double().unsqueeze(1)
+        r = tw_rows_of(self.kind, self.pred, y1, x.reshape(1, -1), self.u, self.c, self.xi)
+        valid = ok.sum().double().reshape(1)
+        mean = torch.where(ok.unsqueeze(1), r, torch.zeros_like(r)).sum(0) / valid
+        out = torch.where(ok.unsqueeze(1), r, torch.full_like(r, float("nan"))) if rows else None
+        return TwScore(mean, valid, out, x)
+
     def _rows(self):
         """Columns [N, 1] in fp64 and the per-row invariants of the kernel's RowP."""
         P = self.pred.double()

@@ -176,6 +176,96 @@ class _FusedCRPS(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None, None
 
 
+class _FusedTwCRPS(torch.autograd.Function):
+    """:class:`_FusedCRPS` for ``(1 - tw_weight) * CRPS + tw_weight * twCRPS`` at ``tw_threshold``
+    (gine_crps_tw_fwd / _fwd_grad / _bwd): the same pass with the threshold-weighted term
+    beside the plain one.  It does not run the head backward: the head's own launch does."""
+
+    @staticmethod
+    def forward(ctx, pred, y, kind, u, xi, c, t, tw_t, tw_w, count_rec=None):
+        needs = ctx.needs_input_grad[0]
+        pred = pred.detach().float().contiguous()
+        y_in = y
+        y = y.detach().float().contiguous()
+        N, K = pred.shape
+        dev = pred.device
+        n_part = ctypes.c_int32(0)
+        _lib.call("gine_crps_num_partials", N, ctypes.byref(n_part))
+        dpred = torch.empty(N, K, dtype=torch.float64, device=dev)
+        partials = torch.empty(n_part.value, 2, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float64, device=dev)
+        count = torch.empty(1, dtype=torch.float64, device=dev)
+        ctx.grad_unit = None
+        if needs and N > 0:
+            count_in = _valid_count(y, count_rec, y_in)
+            ctx.grad_unit = torch.empty(N, K, dtype=torch.float32, device=dev)
+            _lib.call("gine_crps_tw_fwd_grad", _lib.ptr(pred), _lib.ptr(y), N, kind, u, xi, c, t,
+                      tw_t, tw_w, _lib.ptr(dpred), _lib.ptr(partials), _lib.ptr(loss),
+                      _lib.ptr(count), _lib.ptr(_ticket(dev)), _lib.ptr(count_in),
+                      _lib.ptr(ctx.grad_unit), _lib.stream_handle(dev))
+        else:
+            _lib.call("gine_crps_tw_fwd", _lib.ptr(pred), _lib.ptr(y), N, kind, u, xi, c, t, tw_t,
+                      tw_w, _lib.ptr(dpred), _lib.ptr(partials), _lib.ptr(loss), _lib.ptr(count),
+                      _lib.ptr(_ticket(dev)), _lib.stream_handle(dev))
+        ctx.save_for_backward(dpred, count)
+        ctx.kind, ctx.tw = kind, (tw_t, tw_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if ctx.grad_unit is not None and gradbuf.is_unit_seed(gloss):
+            return (ctx.grad_unit,) + (None,) * 9
+        dpred, count = ctx.saved_tensors
+        N = dpred.size(0)
+        g = gloss.detach().to(torch.float64).reshape(1).contiguous()
+        grad = torch.empty(dpred.shape, dtype=torch.float32, device=dpred.device)
+        _lib.call("gine_crps_tw_bwd", _lib.ptr(dpred), _lib.ptr(count), _lib.ptr(g), N, ctx.kind,
+                  ctx.tw[0], ctx.tw[1], _lib.ptr(grad), _lib.stream_handle(dpred.device))
+        return (grad,) + (None,) * 9
+
+
+def _fused_tw(prediction, y, kind, tw_t, tw_w, u=0.0, xi=0.5, c=float(np.log(0.01)), t=5.0):
+    if prediction.dim() != 2:
+        raise ValueError("prediction must be [N, K]")
+    return _FusedTwCRPS.apply(prediction, y, kind, float(u), float(xi), float(c), float(t),
+                              float(tw_t), float(tw_w), _head.record_of(prediction))
+
+
+class _TwMixin:
+    """The optional threshold-weighted term of a loss class: ``tw_threshold`` (model space) and
+    ``tw_weight`` in [0, 1]; the per-row loss becomes ``(1 - tw_weight) * L + tw_weight *
+    twCRPS_t`` (:mod:`raincast_gnn.twcrps`).  Off (``None`` or weight 0): ``crps()`` is the
+    plain loss's code, launch for launch."""
+
+    def _init_tw(self, tw_threshold, tw_weight):
+        tw_weight = float(tw_weight)
+        if not 0.0 <= tw_weight <= 1.0:
+            raise ValueError(f"tw_weight must lie in [0, 1], got {tw_weight!r}")
+        if tw_threshold is not None:
+            tw_threshold = float(tw_threshold)
+            if not math.isfinite(tw_threshold):
+                raise ValueError(f"tw_threshold must be finite, got {tw_threshold!r}")
+        self.tw_threshold, self.tw_weight = tw_threshold, tw_weight
+
+    @property
+    def tw_on(self) -> bool:
+        return self.tw_threshold is not None and self.tw_weight != 0.0
+
+    def _tw_finish(self, plain, mask, kind, prediction, y1, u_fixed, c, xi, reduce):
+        """``plain [N, 1]``: the plain per-row loss of the torch formulation."""
+        from .twcrps import tw_rows_of
+        t = torch.full((1, 1), self.tw_threshold, dtype=torch.float64, device=y1.device)
+        tw = tw_rows_of(kind, prediction, y1, t, u_fixed, c, xi)
+        if self.tw_weight != 1.0:  # (at 1 the plain rows are not part of the autograd graph)
+            tw = (1.0 - self.tw_weight) * plain.double() + self.tw_weight * tw
+        return _finish(tw, mask, reduce)
+
+
+def tw_threshold_from_mm(mm: float) -> float:
+    """A threshold in millimetres as the model-space value ``log(mm + 0.01)``."""
+    return math.log(float(mm) + 0.01)
+
+
 def _fused(prediction, y, kind, u=0.0, xi=0.5, c=float(np.log(0.01)), t=5.0):
     if prediction.dim() != 2:
         raise ValueError("prediction must be [N, K]")
@@ -202,33 +292,49 @@ def _prepare(prediction: torch.Tensor, y: torch.Tensor, width: int):
     return mask, cols, y_safe
 
 
-class NormalCRPS(torch.nn.Module):
+class NormalCRPS(_TwMixin, torch.nn.Module):
     """models/loss.py:335-369.  ``fused`` (every loss class): False keeps the torch
-    formulation on a HIP device too (the drop-in model, raincast_gnn/dropin.py)."""
+    formulation on a HIP device too (the drop-in model, raincast_gnn/dropin.py).
+    ``tw_threshold`` / ``tw_weight`` (every loss class): :class:`_TwMixin`."""
 
     fused = True
 
+    def __init__(self, *, tw_threshold: float | None = None, tw_weight: float = 0.0):
+        super().__init__()
+        self._init_tw(tw_threshold, tw_weight)
+
     def crps(self, prediction: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         # the reference's NormalCRPS stays fp32 (loss.py:358-369)
+        if self.tw_on and _use_fused(prediction, True, self.fused):
+            return _fused_tw(prediction, y, _lib.LOSS_NORMAL, self.tw_threshold,
+                             self.tw_weight).to(torch.float32)
         if _use_fused(prediction, True, self.fused):
             return _fused(prediction, y, _lib.LOSS_NORMAL).to(torch.float32)
         mask, (mu, sigma), y1 = _prepare(prediction, y, 2)
         z = (y1 - mu) / sigma
         crps = sigma * (z * (2.0 * _cdf(z) - 1.0) + 2.0 * _pdf(z) - _INV_SQRT_PI_F32)
+        if self.tw_on:
+            return self._tw_finish(crps, mask, _lib.LOSS_NORMAL, prediction, y1, None,
+                                   float(np.log(0.01)), 0.5, True).to(torch.float32)
         return _finish(crps, mask, True)
 
 
-class MixedNormalCRPS(torch.nn.Module):
+class MixedNormalCRPS(_TwMixin, torch.nn.Module):
     """Censored normal with a point mass p at c, models/loss.py:6-68."""
 
     fused = True
 
-    def __init__(self, reduce: bool = True, c: float = np.log(0.01)):
+    def __init__(self, reduce: bool = True, c: float = np.log(0.01), *,
+                 tw_threshold: float | None = None, tw_weight: float = 0.0):
         super().__init__()
         self.reduce = reduce
         self.c = c
+        self._init_tw(tw_threshold, tw_weight)
 
     def crps(self, prediction: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        if self.tw_on and _use_fused(prediction, self.reduce, self.fused):
+            return _fused_tw(prediction, y, _lib.LOSS_MIXED_NORMAL, self.tw_threshold,
+                             self.tw_weight, c=float(self.c))
         if _use_fused(prediction, self.reduce, self.fused):
             return _fused(prediction, y, _lib.LOSS_MIXED_NORMAL, c=float(self.c))
         mask, (mu, sigma, p), y1 = _prepare(prediction, y, 3)
@@ -243,18 +349,22 @@ class MixedNormalCRPS(torch.nn.Module):
         t5 = (2 * torch.pow(1 - p, 2) * (-1 / (2 * math.sqrt(math.pi)))
               * (1 - _cdf(math.sqrt(2) * c_t)))
         crps = sigma * (t1 + t2 + t3 + t4 + t5)
+        if self.tw_on:
+            return self._tw_finish(crps, mask, _lib.LOSS_MIXED_NORMAL, prediction, y1, None,
+                                   float(self.c), 0.5, self.reduce)
         return _finish(crps, mask, self.reduce)
 
 
-class MixedLoss(torch.nn.Module):
+class MixedLoss(_TwMixin, torch.nn.Module):
     """Censored normal body + generalised Pareto tail above u, models/loss.py:71-272."""
 
     fused = True
 
     def __init__(self, grad_u: bool, xi: float, u=None, reduce: bool = True, t: float = 5,
-                 c=np.log(0.01)):
+                 c=np.log(0.01), *, tw_threshold: float | None = None, tw_weight: float = 0.0):
         super().__init__()
         self.reduce, self.c, self.grad_u, self.u, self.xi, self.t = reduce, c, grad_u, u, xi, t
+        self._init_tw(tw_threshold, tw_weight)
 
     @staticmethod
     def _gpd(x_re, xi):
@@ -292,6 +402,11 @@ class MixedLoss(torch.nn.Module):
         return sigma * (u_t + t2 + t3 + t4 + t5)
 
     def crps(self, prediction: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        if self.tw_on and _use_fused(prediction, self.reduce, self.fused):
+            kind = _lib.LOSS_MIXED_U if self.grad_u else _lib.LOSS_MIXED
+            u = 0.0 if self.grad_u else float(np.float32(self.u))
+            return _fused_tw(prediction, y, kind, self.tw_threshold, self.tw_weight, u=u,
+                             xi=float(np.float32(self.xi)), c=float(self.c), t=float(self.t))
         if _use_fused(prediction, self.reduce, self.fused):
             # u / xi are fp32 tensors in the reference (torch.tensor([python float]))
             kind = _lib.LOSS_MIXED_U if self.grad_u else _lib.LOSS_MIXED
@@ -317,4 +432,9 @@ class MixedLoss(torch.nn.Module):
             crps = torch.sigmoid((u - y1) * self.t) * (loss_1 - loss_2) + loss_2
         else:
             crps = torch.where(y1 < u, loss_1, loss_2)
+        if self.tw_on:  # u / xi rounded to fp32 as the reference's tensors are
+            kind = _lib.LOSS_MIXED_U if self.grad_u else _lib.LOSS_MIXED
+            u_fixed = None if self.grad_u else float(np.float32(self.u))
+            return self._tw_finish(crps, mask, kind, prediction, y1, u_fixed, float(self.c),
+                                   float(np.float32(self.xi)), self.reduce)
         return _finish(crps, mask, self.reduce)

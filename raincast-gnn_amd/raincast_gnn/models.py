@@ -84,16 +84,18 @@ class DeepSetEncoder(nn.Module):
         return self.rho(phi_sum)
 
 
-def make_loss(loss: str, grad_u, u, xi):
-    """gnn.py:91-103: loss object and number of distribution parameters."""
+def make_loss(loss: str, grad_u, u, xi, tw_threshold=None, tw_weight=0.0):
+    """gnn.py:91-103: loss object and number of distribution parameters.  ``tw_threshold``
+    (model space) / ``tw_weight``: the optional threshold-weighted term (raincast_gnn.loss)."""
+    tw = dict(tw_threshold=tw_threshold, tw_weight=tw_weight)
     if loss == "NormalCRPS":
-        return NormalCRPS(), 2
+        return NormalCRPS(**tw), 2
     if loss == "MixedNormalCRPS":
-        return MixedNormalCRPS(), 3
+        return MixedNormalCRPS(**tw), 3
     if loss == "MixedLoss":
         if grad_u == "True":
-            return MixedLoss(grad_u=True, xi=xi), 5
-        return MixedLoss(grad_u=False, u=u, xi=xi), 4
+            return MixedLoss(grad_u=True, xi=xi, **tw), 5
+        return MixedLoss(grad_u=False, u=u, xi=xi, **tw), 4
     raise ValueError(f"unknown loss '{loss}'")
 
 
@@ -103,10 +105,10 @@ class GNN(nn.Module):
 
     def __init__(self, in_channels, hidden_channels_gnn, out_channels_gnn, num_layers_gnn,
                  optimizer_class=None, optimizer_params=None, loss="MixedLoss", grad_u=False,
-                 u=0.5, xi=0.5, edge_dim=1):
+                 u=0.5, xi=0.5, edge_dim=1, tw_threshold=None, tw_weight=0.0):
         super().__init__()
         self.loss, self.grad_u, self.u, self.xi = loss, grad_u, u, xi
-        self.loss_fn, self.out_channels = make_loss(loss, grad_u, u, xi)
+        self.loss_fn, self.out_channels = make_loss(loss, grad_u, u, xi, tw_threshold, tw_weight)
         self.deepset = DeepSetEncoder(ensemble_in_dim=in_channels,
                                       hidden_channels=hidden_channels_gnn,
                                       out_channels=hidden_channels_gnn)
@@ -165,12 +167,16 @@ class GNN(nn.Module):
 
 
 def gnn_from_params(params: dict, in_channels: int = 35, **overrides) -> GNN:
-    """Build the model the way train.py:168-179 does from a params.json dict (plus an
-    optional "edge_dim" key, default 1)."""
+    """Build the model the way train.py:168-179 does from a params.json dict (plus the
+    optional keys "edge_dim", default 1, and "tw_threshold_mm" / "tw_weight": the
+    threshold-weighted loss term, off by default)."""
+    from .params import tw_from_params
     cfg = dict(params)
     cfg.update(overrides)
+    tw_threshold, tw_weight = tw_from_params(cfg)
     return GNN(in_channels=in_channels, hidden_channels_gnn=cfg["gnn_hidden"],
                out_channels_gnn=cfg["gnn_hidden"], num_layers_gnn=cfg["gnn_layers"],
                optimizer_class=torch.optim.AdamW, optimizer_params={"lr": cfg["lr"]},
                loss=cfg["loss"], grad_u=cfg["grad_u"], u=cfg["u"], xi=cfg["xi"],
-               edge_dim=int(cfg.get("edge_dim", 1)))
+               edge_dim=int(cfg.get("edge_dim", 1)), tw_threshold=tw_threshold,
+               tw_weight=tw_weight)

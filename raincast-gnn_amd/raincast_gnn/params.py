@@ -9,6 +9,7 @@ BASELINE.json / SURVEY.md section 8.
 from __future__ import annotations
 
 import json
+import math
 from dataclasses import dataclass, replace
 
 _COMMON = {"batch_size": 8, "gnn_hidden": 128, "gnn_layers": 4, "heads": 8, "lr": 0.0001,
@@ -57,10 +58,29 @@ def check_optimizer_keys(params: dict) -> None:
                 raise ValueError(f"params.json lr_schedule {k}={s[k]!r}: expected a number >= 0")
 
 
+def tw_from_params(params: dict):
+    """The optional threshold-weighted loss term of a ``params.json``: ``tw_threshold_mm`` (a
+    threshold in millimetres, > -0.01) and ``tw_weight`` (in [0, 1]) -> ``(tw_threshold,
+    tw_weight)`` with the threshold in model space ``log(mm + 0.01)``; ``(None, 0.0)`` when the
+    keys are absent (none of the reference's files has them)."""
+    mm, w = params.get("tw_threshold_mm"), params.get("tw_weight", 0.0)
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= w <= 1.0:
+        raise ValueError(f"params.json tw_weight={w!r}: expected a number in [0, 1]")
+    if mm is None:
+        if w != 0.0:
+            raise ValueError("params.json has tw_weight but no tw_threshold_mm")
+        return None, 0.0
+    if isinstance(mm, bool) or not isinstance(mm, (int, float)) or not mm > -0.01 \
+            or mm == float("inf"):
+        raise ValueError(f"params.json tw_threshold_mm={mm!r}: expected a finite number > -0.01")
+    return math.log(mm + 0.01), float(w)
+
+
 def load_params(path: str) -> dict:
     with open(path) as f:
         params = json.load(f)
     check_optimizer_keys(params)
+    tw_from_params(params)
     return params
 
 

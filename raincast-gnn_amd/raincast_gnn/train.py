@@ -240,7 +240,17 @@ def train_one_epoch(model, loader, optimizer, device, logger=None, runner=None) 
 def evaluate(model, loader, device, logger=None) -> float:
     """train.py:76-91: eval mode (BatchNorm from running statistics), mean batch loss."""
     model.eval()
-    losses = [model.loss_fn.crps(model(b.to(device)), b.to(device).y) for b in loader]
+    tw = getattr(model.loss_fn, "tw_on", False)  # a threshold-weighted loss: log its two parts
+    losses, parts = [], []
+    for b in loader:
+        b = b.to(device)
+        pred = model(b)
+        losses.append(model.loss_fn.crps(pred, b.y))
+        if tw:
+            from .forecast import Forecast
+            fc = Forecast.from_model(model, pred)
+            parts.append(torch.stack([fc.score(b.y).crps,
+                                      fc.twcrps(b.y, [model.loss_fn.tw_threshold]).mean[0]]))
     if not losses:
         raise ValueError("the validation loader yielded no batch")
     total = 0.0
@@ -248,6 +258,10 @@ def evaluate(model, loader, device, logger=None) -> float:
         total += v
     avg = total / len(losses)
     (logger or log).info(f"  [Val] Loss: {avg:.6f}")
+    if tw:
+        crps, twc = torch.stack(parts).mean(0).cpu().tolist()
+        (logger or log).info(f"  [Val] CRPS: {crps:.6f}, twCRPS(t={model.loss_fn.tw_threshold:.4f},"
+                             f" weight {model.loss_fn.tw_weight:g}): {twc:.6f}")
     return avg
 
 
@@ -386,10 +400,20 @@ def main(argv=None) -> dict:
                     help="linear warm-up steps of --schedule cosine / linear")
     ap.add_argument("--resume", metavar="PATH", default=None,
                     help="a run_<id>-best.ckpt to continue from (with the .opt beside it)")
+    ap.add_argument("--tw-threshold-mm", type=float, default=None,
+                    help="threshold (mm) of the threshold-weighted CRPS term of the loss "
+                         "(params.json tw_threshold_mm)")
+    ap.add_argument("--tw-weight", type=float, default=None,
+                    help="weight in [0, 1] of that term: (1 - w) CRPS + w twCRPS (params.json "
+                         "tw_weight); the best checkpoint is still chosen by the validation loss")
     args = ap.parse_args(argv)
 
     rank, local_rank, world = env_rank()
     config = load_params(os.path.join(args.dir, "params.json"))
+    if args.tw_threshold_mm is not None:
+        config["tw_threshold_mm"] = args.tw_threshold_mm
+    if args.tw_weight is not None:
+        config["tw_weight"] = args.tw_weight
     bs = config["batch_size"]
     if world > 1 and bs % world:
         # DeviceLoader's condition (equal shards in every full batch), reported up front
