@@ -55,7 +55,9 @@ extern "C" {
                                   scores and ECC members,
                                   gine_forecast_twcrps(_partials) / gine_ensemble_twcrps /
                                   gine_crps_tw_fwd / _fwd_grad / _bwd: the threshold-weighted
-                                  CRPS as a score and as a loss term */
+                                  CRPS as a score and as a loss term,
+                                  gine_field_energy / _variogram / _area(_partials): member
+                                  fields scored per graph */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -867,6 +869,59 @@ int gine_crps_tw_fwd_grad(const float* pred, const float* y, int64_t num_nodes, 
 int gine_crps_tw_bwd(const double* dpred, const double* count, const double* gloss,
                      int64_t num_nodes, int32_t kind, double tw_threshold, double tw_weight,
                      float* grad_pred, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Member fields scored per graph (csrc/gine_field.hip): members [N, M], M <= 64,
+ * against targets y [N] fp32 (NaN = missing); the rows of graph g are ptr[g] .. ptr[g+1]-1
+ * (ptr [G+1] int64 on the device, ptr[0] = 0, non-decreasing, ptr[G] = num_rows).  Member i of
+ * row n is  x = shift + scale * (double)members[n * row_stride + i * member_stride]  (strides in
+ * elements, >= 0), the element fp32 (GINE_FIELD_F32: the raw ensemble, read in place) or fp64
+ * (GINE_FIELD_F64: the output of gine_ensemble_ecc).  Per graph, S = the rows with a non-NaN
+ * target and at least one non-NaN member, V = the members non-NaN at every row of S (all M for
+ * an empty S): rows_valid = |S|, members_valid = m = |V|, never NaN; every score is NaN when S
+ * is empty or m = 0.  All [G] outputs fp64; each may be NULL.
+ * gine_field_energy:  es = (1/m) sum_i |X_i - y| - (1/(2 m^2)) sum_ij |X_i - X_j|, |.| the
+ *   Euclidean norm over S and i, j in V; es_fair with 1/(2 m (m - 1)), NaN for m < 2.
+ * gine_field_variogram: vs = sum over the pairs a < b of S of
+ *   (|y_a - y_b|^p - (1/m) sum_i |X_ai - X_bi|^p)^2, pairs = |S| (|S| - 1) / 2; p > 0 finite
+ *   (0.5, 1 and 2 take sqrt, abs and the square, any other p pow).
+ * gine_field_area: A_i = the max (GINE_FIELD_MAX) or mean (GINE_FIELD_MEAN) over S of
+ *   mm(x) = max(exp(x) - 0.01, 0) for i in V (NaN otherwise) -> members_out [G, M]; obs = the
+ *   same of mm(y); crps / crps_fair / rank_lo / rank_hi of gine_ensemble_score on (A, obs).
+ * partials: gine_field_*_partials doubles of workspace (0 for the area: partials may be NULL
+ *   there).  GINE_FIELD_ROW_TILE rows make one tile of the energy and variogram kernels.
+ * GINE_ERR_INVALID, before any HIP call, for num_members outside 1..64, a negative size or
+ * stride, an unknown dtype or stat, p <= 0 or not finite, or a NULL members / y / ptr /
+ * partials.  num_graphs = 0 or num_rows = 0: GINE_OK, nothing launched, nothing written.  No
+ * allocation, no host synchronisation (capturable); every sum fp64 in a fixed order, no
+ * floating-point atomics (same bits every run).
+ * ---------------------------------------------------------------------------------- */
+#define GINE_FIELD_F32 0
+#define GINE_FIELD_F64 1
+#define GINE_FIELD_MAX 0
+#define GINE_FIELD_MEAN 1
+#define GINE_FIELD_ROW_TILE 64
+int gine_field_energy_partials(int64_t num_rows, int64_t num_graphs, int32_t num_members,
+                               size_t* count);
+int gine_field_variogram_partials(int64_t num_rows, int64_t num_graphs, size_t* count);
+int gine_field_area_partials(int64_t num_rows, int64_t num_graphs, size_t* count);
+int gine_field_energy(const void* members, int32_t dtype, int64_t row_stride,
+                      int64_t member_stride, int32_t num_members, double scale, double shift,
+                      const float* y, int64_t num_rows, const int64_t* ptr, int64_t num_graphs,
+                      double* es, double* es_fair, double* members_valid, double* rows_valid,
+                      double* partials, void* stream);
+int gine_field_variogram(const void* members, int32_t dtype, int64_t row_stride,
+                         int64_t member_stride, int32_t num_members, double scale, double shift,
+                         const float* y, int64_t num_rows, const int64_t* ptr,
+                         int64_t num_graphs, double p, double* vs, double* pairs,
+                         double* members_valid, double* rows_valid, double* partials,
+                         void* stream);
+int gine_field_area(const void* members, int32_t dtype, int64_t row_stride,
+                    int64_t member_stride, int32_t num_members, double scale, double shift,
+                    const float* y, int64_t num_rows, const int64_t* ptr, int64_t num_graphs,
+                    int32_t stat, double* members_out, double* obs, double* crps,
+                    double* crps_fair, double* rank_lo, double* rank_hi, double* members_valid,
+                    double* rows_valid, double* partials, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Weight/bias gradient of a plain Linear y = x W^T + b over many rows (the DeepSet,

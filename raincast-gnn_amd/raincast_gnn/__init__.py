@@ -11,10 +11,11 @@ from .nn import GINEConv
 from .inference import Predictor
 from .forecast import Forecast, ForecastScore, TwScore, pit_sample
 from .ensemble import EnsembleScore, EnsembleTwScore, RawEnsemble, skill
+from .fields import AreaScore, FieldScore, MemberFields
 
-__all__ = ["EnsembleScore", "EnsembleTwScore", "Forecast", "ForecastScore", "GINEConv",
-           "GineGraph", "Predictor", "RawEnsemble", "TwScore", "get_graph", "graph_cache",
-           "native_library", "pit_sample", "skill"]
+__all__ = ["AreaScore", "EnsembleScore", "EnsembleTwScore", "FieldScore", "Forecast",
+           "ForecastScore", "GINEConv", "GineGraph", "MemberFields", "Predictor", "RawEnsemble",
+           "TwScore", "get_graph", "graph_cache", "native_library", "pit_sample", "skill"]
 
 
 def native_library():

@@ -29,6 +29,9 @@ COUNT_PARTS = 64  # GINE_COUNT_PARTS
 FORECAST_UPPER = 1  # GINE_FORECAST_UPPER
 ECC_MIDPOINT = 1  # GINE_ECC_MIDPOINT
 ENSEMBLE_MAX_MEMBERS = 64  # gine_ensemble_*: one wavefront per row
+FIELD_F32, FIELD_F64 = 0, 1  # GINE_FIELD_F32 / GINE_FIELD_F64
+FIELD_MAX, FIELD_MEAN = 0, 1  # GINE_FIELD_MAX / GINE_FIELD_MEAN
+FIELD_ROW_TILE = 64  # GINE_FIELD_ROW_TILE
 
 _c_void_p = ctypes.c_void_p
 _i32, _i64, _f32, _size = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
@@ -196,6 +199,15 @@ _SIGNATURES = {
     "gine_crps_tw_fwd_grad": [_c_void_p, _c_void_p, _i64, _i32] + [_f64] * 6 + [_c_void_p] * 8,
     "gine_crps_tw_bwd": [_c_void_p, _c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _c_void_p,
                          _c_void_p],
+    "gine_field_energy_partials": [_i64, _i64, _i32, ctypes.POINTER(_size)],
+    "gine_field_variogram_partials": [_i64, _i64, ctypes.POINTER(_size)],
+    "gine_field_area_partials": [_i64, _i64, ctypes.POINTER(_size)],
+    "gine_field_energy": [_c_void_p, _i32, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64,
+                          _c_void_p, _i64] + [_c_void_p] * 6,
+    "gine_field_variogram": [_c_void_p, _i32, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64,
+                             _c_void_p, _i64, _f64] + [_c_void_p] * 6,
+    "gine_field_area": [_c_void_p, _i32, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64,
+                        _c_void_p, _i64, _i32] + [_c_void_p] * 10,
     "gine_linear_wgrad_num_chunks": [_i64, _i32, _i32, ctypes.POINTER(_i32)],
     "gine_linear_wgrad": [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p,
                           _c_void_p, _f32, _c_void_p],

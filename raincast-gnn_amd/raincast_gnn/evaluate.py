@@ -110,6 +110,52 @@ def verify_against_ensemble(model: torch.nn.Module, preds: torch.Tensor, targets
 
 
 @dataclass
+class FieldVerification:
+    """What :func:`verify_fields` returns: the :class:`raincast_gnn.fields.FieldScore` of the
+    model's ECC members and of the raw ensemble, and the skills ``1 - model / ensemble`` of the
+    mean energy score, the mean variogram score and the mean area CRPS, each mean over the
+    ``valid`` graphs (those with a value in both)."""
+    model: object
+    ensemble: object
+    energy_skill: torch.Tensor
+    variogram_skill: torch.Tensor
+    area_skill: torch.Tensor
+    valid: torch.Tensor
+
+
+def verify_fields(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor, raw, ptr,
+                  p: float = 0.5, levels: str = "uniform",
+                  stat: str = "max") -> FieldVerification:
+    """The model's predictions as fields beside the raw ensemble's: the predictive distribution
+    turned back into members by ECC (``Forecast.ecc(raw, levels)``), both sets of members
+    scored per graph of ``ptr`` (``GraphBatch.ptr``) by :class:`raincast_gnn.fields.MemberFields`
+    -- energy score, variogram score of order ``p``, CRPS of the area ``stat`` in mm -- and the
+    three skills, means over the graphs valid in both as :func:`verify_against_ensemble` does
+    per row."""
+    from .ensemble import skill
+    from .fields import MemberFields
+    from .forecast import Forecast
+    members = Forecast.from_model(model, preds).ecc(raw, levels=levels)
+    y = targets.to(raw.device)
+    raw_fields = MemberFields.from_raw(raw, torch.as_tensor(ptr).to(raw.device))
+    es = raw_fields.score(y, p=p, stat=stat)
+    ms = raw_fields.with_members(members).score(y, p=p, stat=stat)
+
+    def mean_skill(a, b):
+        b = b.to(a.device)
+        both = ~torch.isnan(a) & ~torch.isnan(b)
+        zero = torch.zeros_like(a)
+        count = both.sum().double()
+        return skill(torch.where(both, a, zero).sum() / count,
+                     torch.where(both, b, zero).sum() / count), count
+
+    energy, valid = mean_skill(ms.es, es.es)
+    vario, _ = mean_skill(ms.vs, es.vs)
+    area, _ = mean_skill(ms.area.crps, es.area.crps)
+    return FieldVerification(ms, es, energy, vario, area, valid)
+
+
+@dataclass
 class TwVerification:
     """What :func:`verify_tw` returns, per threshold: the model's and the raw ensemble's mean
     twCRPS over the ``valid`` rows (those with a value in both), and the skill
