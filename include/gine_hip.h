@@ -57,7 +57,9 @@ extern "C" {
                                   gine_crps_tw_fwd / _fwd_grad / _bwd: the threshold-weighted
                                   CRPS as a score and as a loss term,
                                   gine_field_energy / _variogram / _area(_partials): member
-                                  fields scored per graph */
+                                  fields scored per graph,
+                                  gine_batch_fill_permuted: a batch with permuted feature
+                                  columns written into a forward's inputs */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -922,6 +924,29 @@ int gine_field_area(const void* members, int32_t dtype, int64_t row_stride,
                     int32_t stat, double* members_out, double* obs, double* crps,
                     double* crps_fair, double* rank_lo, double* rank_hi, double* members_valid,
                     double* rows_valid, double* partials, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Batch assembly with permuted feature columns (csrc/gine_batch.hip; the
+ * reference's utils/data.py shuffle_features applied to station features and ensemble alike):
+ * B samples of a device-resident dataset x [T, N, F], ens [T, N, M, F], y [T, N] written as one
+ * collated batch out_x [B*N, F], out_ens [B*N, M, F], out_y [B*N].  With t = idx[b] (idx [B]
+ * int64 on the device), slot b, station i, column f is read from
+ *   (perm_t[t], perm_n[t * N + i])  when bit f of col_mask is set,   (t, i)  otherwise,
+ * for x and for every member of ens; out_y[b, i] = y[t, i].  perm_t [T] int64 and perm_n [T, N]
+ * int32 (positions as the dataset stores them) are device arrays; either may be NULL = the
+ * identity.  The indices are trusted: the caller has checked that they are in range.
+ * One launch, every access one dword per lane, 64-bit offsets; no allocation, no host
+ * synchronisation (capturable).  Before any HIP call: GINE_ERR_INVALID for a negative size,
+ * N, M or F below 1, T = 0 with B > 0, a NULL x / ens / y / idx / output, a col_mask bit at or
+ * above F, or a non-zero col_mask with both permutations NULL; GINE_ERR_DIM for F > 64 (the
+ * mask's width); GINE_ERR_TOO_LARGE for M * F > 2^31 - 513 or B * ceil(N / 4) >= 2^31.
+ * B = 0: GINE_OK, nothing launched.
+ * ---------------------------------------------------------------------------------- */
+int gine_batch_fill_permuted(const float* x, const float* ens, const float* y,
+                             const int64_t* idx, const int64_t* perm_t, const int32_t* perm_n,
+                             uint64_t col_mask, int64_t T, int32_t N, int32_t M, int32_t F,
+                             int32_t B, float* out_x, float* out_ens, float* out_y,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Weight/bias gradient of a plain Linear y = x W^T + b over many rows (the DeepSet,

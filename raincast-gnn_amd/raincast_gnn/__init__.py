@@ -12,10 +12,13 @@ from .inference import Predictor
 from .forecast import Forecast, ForecastScore, TwScore, pit_sample
 from .ensemble import EnsembleScore, EnsembleTwScore, RawEnsemble, skill
 from .fields import AreaScore, FieldScore, MemberFields
+from .importance import (FEATURE_NAMES, FeatureImportance, PermutationPlan, fill_batch,
+                         permutation_importance)
 
-__all__ = ["AreaScore", "EnsembleScore", "EnsembleTwScore", "FieldScore", "Forecast",
-           "ForecastScore", "GINEConv", "GineGraph", "MemberFields", "Predictor", "RawEnsemble",
-           "TwScore", "get_graph", "graph_cache", "native_library", "pit_sample", "skill"]
+__all__ = ["AreaScore", "EnsembleScore", "EnsembleTwScore", "FEATURE_NAMES", "FeatureImportance",
+           "FieldScore", "Forecast", "ForecastScore", "GINEConv", "GineGraph", "MemberFields",
+           "PermutationPlan", "Predictor", "RawEnsemble", "TwScore", "fill_batch", "get_graph",
+           "graph_cache", "native_library", "permutation_importance", "pit_sample", "skill"]
 
 
 def native_library():

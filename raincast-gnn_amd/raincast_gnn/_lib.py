@@ -32,6 +32,7 @@ ENSEMBLE_MAX_MEMBERS = 64  # gine_ensemble_*: one wavefront per row
 FIELD_F32, FIELD_F64 = 0, 1  # GINE_FIELD_F32 / GINE_FIELD_F64
 FIELD_MAX, FIELD_MEAN = 0, 1  # GINE_FIELD_MAX / GINE_FIELD_MEAN
 FIELD_ROW_TILE = 64  # GINE_FIELD_ROW_TILE
+BATCH_MAX_FEATURES = 64  # gine_batch_fill_permuted: the bits of col_mask
 
 _c_void_p = ctypes.c_void_p
 _i32, _i64, _f32, _size = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
@@ -208,6 +209,8 @@ _SIGNATURES = {
                              _c_void_p, _i64, _f64] + [_c_void_p] * 6,
     "gine_field_area": [_c_void_p, _i32, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64,
                         _c_void_p, _i64, _i32] + [_c_void_p] * 10,
+    "gine_batch_fill_permuted": [_c_void_p] * 6 + [ctypes.c_uint64, _i64, _i32, _i32, _i32, _i32,
+                                                   _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "gine_linear_wgrad_num_chunks": [_i64, _i32, _i32, ctypes.POINTER(_i32)],
     "gine_linear_wgrad": [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p,
                           _c_void_p, _f32, _c_void_p],

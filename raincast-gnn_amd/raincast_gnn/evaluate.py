@@ -155,6 +155,14 @@ def verify_fields(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Te
     return FieldVerification(ms, es, energy, vario, area, valid)
 
 
+def feature_importance(model: torch.nn.Module, dataset, **kw):
+    """Which inputs the model uses: the permutation importance of each feature group of
+    ``dataset`` (a :class:`raincast_gnn.batching.DeviceDataset`) in CRPS, and in twCRPS with
+    ``thresholds``; :func:`raincast_gnn.importance.permutation_importance` with its keywords."""
+    from .importance import permutation_importance
+    return permutation_importance(model, dataset, **kw)
+
+
 @dataclass
 class TwVerification:
     """What :func:`verify_tw` returns, per threshold: the model's and the raw ensemble's mean

@@ -240,10 +240,45 @@ class Predictor:
         graph.replay()
         return out.clone()
 
-    def _capture(self, batch) -> tuple:
-        static = GraphBatch(batch.x.clone(), batch.ensemble.clone(), batch.edge_index,
-                            batch.edge_attr, batch.y, batch.batch, batch.ptr, batch.num_graphs,
-                            dict(batch.extra))
+    @torch.no_grad()
+    def bind(self, batch: GraphBatch) -> "BoundForward":
+        """A handle on the forward of ``batch``'s (``edge_index`` object, N): its static ``x``
+        and ``ensemble`` are written in place by the caller and ``run()`` returns the static
+        output, so a loop that assembles its own batches pays no copy around the replay.  The
+        warm-up calls and the capture happen here if they have not happened yet; the capture is
+        the one ``predictor(batch)`` replays for this edge list, so a call to it overwrites the
+        handle's inputs."""
+        self.model.eval()
+        return BoundForward(self, batch)
+
+    def _bound_capture(self, batch, static=None) -> tuple | None:
+        """The live capture for ``batch`` -- warmed up and captured now if need be, into
+        ``static``'s tensors when given -- or None where ``__call__`` would not capture."""
+        if not self.capture or not batch.x.is_cuda or not self._is_gnn():
+            return None
+        ptrs = self._storage_ptrs()
+        if ptrs != self._ptrs:
+            self._slots.clear()
+            self._ptrs = ptrs
+        key = (id(batch.edge_index), batch.x.size(0))
+        slot = self._slots.get(key)
+        if slot is None or slot[0] is not batch.edge_index or slot[1] is not batch.edge_attr:
+            slot = self._slots[key] = [batch.edge_index, batch.edge_attr, 0, None]
+            while len(self._slots) > max(self.max_captures, 1):
+                self._slots.popitem(last=False)
+        self._slots.move_to_end(key)
+        while slot[2] < self.warmup:
+            self._forward(batch)
+            slot[2] += 1
+        if slot[3] is None or static is not None:
+            slot[3] = self._capture(batch, static)
+        return slot[3]
+
+    def _capture(self, batch, static=None) -> tuple:
+        if static is None:
+            static = GraphBatch(batch.x.clone(), batch.ensemble.clone(), batch.edge_index,
+                                batch.edge_attr, batch.y, batch.batch, batch.ptr,
+                                batch.num_graphs, dict(batch.extra))
         self._forward(static)  # the graph's CSR and every size query exist before the capture
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -251,6 +286,60 @@ class Predictor:
         with torch.cuda.graph(graph):
             out = self._forward(static, held)
         return graph, static, out, held
+
+
+class BoundForward:
+    """What :meth:`Predictor.bind` returns: ``x [N, F]`` and ``ensemble [N, M, F]`` are the
+    forward's inputs, to be filled in place; ``run()`` computes ``predictor(batch)`` of what they
+    hold and returns the output tensor itself, valid until the next ``run``.
+
+    On a captured forward ``run()`` is one graph replay.  With ``capture=False``, or a model the
+    Predictor does not capture, the handle owns plain buffers and ``run()`` calls the forward on
+    them.  When a parameter's or buffer's storage has moved since the capture, ``run()`` captures
+    again into the same input tensors first (an in-place ``load_state_dict`` needs nothing)."""
+
+    def __init__(self, predictor: Predictor, batch: GraphBatch):
+        self._predictor = predictor
+        cap = predictor._bound_capture(batch)
+        if cap is not None and (cap[1].x.shape != batch.x.shape
+                                or cap[1].ensemble.shape != batch.ensemble.shape):
+            raise ValueError("bind: this edge list was captured with inputs of another shape")
+        self._set(cap)
+        if cap is None:
+            self._static = GraphBatch(batch.x.clone(), batch.ensemble.clone(), batch.edge_index,
+                                      batch.edge_attr, batch.y, batch.batch, batch.ptr,
+                                      batch.num_graphs, dict(batch.extra))
+            self.out = None
+
+    def _set(self, cap) -> None:
+        self._cap = cap
+        if cap is not None:
+            self._graph, self._static, self.out = cap[0], cap[1], cap[2]
+            self._ptrs = self._predictor._ptrs
+
+    @property
+    def captured(self) -> bool:
+        return self._cap is not None
+
+    @property
+    def x(self) -> torch.Tensor:
+        return self._static.x
+
+    @property
+    def ensemble(self) -> torch.Tensor:
+        return self._static.ensemble
+
+    @torch.no_grad()
+    def run(self) -> torch.Tensor:
+        p = self._predictor
+        p.model.eval()
+        if self._cap is None:
+            self.out = p._forward(self._static)
+            return self.out
+        if p._storage_ptrs() != self._ptrs:  # what was captured reads freed storage
+            self._set(p._bound_capture(self._static, self._static))
+        self._graph.replay()
+        return self.out
 
 
 def predictor_for(model: torch.nn.Module) -> Predictor:
