@@ -1004,6 +1004,23 @@ int gine_deepset_bwd_num_partials(int64_t num_nodes, int32_t hidden, int32_t* nu
 int gine_deepset_bwd(const float* ens, const uint16_t* mask, const float* dr, float* slab,
                      float* dw1, float* db1, int64_t num_nodes, int32_t members,
                      int32_t in_features, int32_t hidden, void* stream);
+/* gine_chain_bwd_folded2 followed by gine_deepset_bwd (the backward of phi[0] -> ReLU ->
+ * member sum -> phi[2] -> rho -> dim_red's embedding columns) as one launch, where
+ * gine_deepset_bwd_chain_ok sets *ok = 1: hidden in {64, 128}, x_features (the width of x,
+ * the chain's F) <= 64, and enough nodes that the DeepSet kernels walk groups of 32 nodes
+ * with one group per workgroup (hidden 128: 8,192 < N <= 16,384; hidden 64: 16,384 < N <=
+ * 32,768; not hidden 64 with 41 to 48 in_features).  Each workgroup computes dt and dr of its own 32 nodes from their dh0 rows (the
+ * chain kernel's arithmetic: dt, the slab, dw1 and db1 are the pair's bits); dt [N, hidden]
+ * is written for gine_chain_wgrad_folded2, dr is not formed in memory.  slab, dw1, db1 as
+ * gine_deepset_bwd (dw1 = NULL leaves the slab; job: gine_deepset_bwd_grad_job).  Any other
+ * shape: GINE_ERR_INVALID -- run the pair. */
+int gine_deepset_bwd_chain_ok(int64_t num_nodes, int32_t hidden, int32_t in_features,
+                              int32_t x_features, int32_t* ok);
+int gine_deepset_bwd_chain(const float* ens, const uint16_t* mask, const float* dh0,
+                           const float* u, const float* wfold, const float* wfold2, float* dt,
+                           float* slab, float* dw1, float* db1, int64_t num_nodes,
+                           int32_t members, int32_t in_features, int32_t hidden,
+                           int32_t x_features, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Output head: aggr = Linear(D, K) + PostProcess (models/gnn.py:123,125,140-141;

@@ -46,6 +46,7 @@
 #include "gine_slab.hpp"
 #include "gine_wgrad.hpp"
 #include "gine_chainfold.hpp"
+#include "gine_chainrow.hpp"  // tile_mma, frag_n
 
 #include <algorithm>
 
@@ -111,24 +112,6 @@ __device__ __forceinline__ floatx16 zero16() {
   return v;
 }
 
-// acc = A[32 x K] (LDS rows, stride lda) x B-fragments (K/2 per lane half)
-template <int K>
-__device__ __forceinline__ floatx16 tile_mma(const float* sA, int lda, const float (&bf)[K / 2],
-                                             int c32, int h) {
-  constexpr int KS = K / 2;
-  floatx16 acc = zero16();
-  const float* arow = sA + c32 * lda + h * KS;
-#pragma unroll
-  for (int q = 0; q < KS / 4; ++q) {
-    const float4 a4 = *reinterpret_cast<const float4*>(&arow[4 * q]);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, bf[4 * q], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, bf[4 * q + 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, bf[4 * q + 2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, bf[4 * q + 3], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
 // Y = X W^T fragment: bf[s] = W[col][h*KS + s]  (W row-major [*, ldw])
 template <int K>
 __device__ __forceinline__ void frag_t(float (&bf)[K / 2], const float* W, int ldw, int col,
@@ -154,14 +137,6 @@ __device__ __forceinline__ void frag_t4(float (&bf)[K / 2], const float* W, int 
     bf[4 * s + 2] = v.z;
     bf[4 * s + 3] = v.w;
   }
-}
-// dX = dY W fragment: bf[s] = W[h*KS + s][coff + col]
-template <int K>
-__device__ __forceinline__ void frag_n(float (&bf)[K / 2], const float* W, int ldw, int coff,
-                                       int col, int h) {
-  constexpr int KS = K / 2;
-#pragma unroll
-  for (int s = 0; s < KS; ++s) bf[s] = W[(size_t)(h * KS + s) * ldw + coff + col];
 }
 // dim_red's weight [D][F + D] seen on the padded k axis [x (F) | 0 (FP - F) | e (D)]
 template <int FP, int D>

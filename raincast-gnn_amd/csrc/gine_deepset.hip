@@ -21,8 +21,10 @@
 #include "gine_common.hpp"
 #include "gine_chainfold.hpp"
 #include "gine_bf16x3.hpp"
+#include "gine_chainrow.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace gine {
 namespace {
@@ -375,13 +377,21 @@ struct Cursor {
 // (never consumed) instead of being skipped, so no register merge at the loop's back edge
 // waits for them (backward 41.4 -> 39.0 us at 16,000 nodes; the forward, whose ring holds
 // no mask word, runs 0.9 us slower that way: profiles/r03_s35).
+// `pro` (k_deepset_bwd_chain): work of the whole workgroup that runs once, after the loads
+// of the walk's first two tiles are issued and before the first of them is staged, so those
+// loads are in flight under it; it may use barriers and must leave buf0 / buf1 alone.
+struct NoPrologue {
+  __device__ __forceinline__ void operator()() const {}
+};
 template <bool UNCOND, bool MASKIN, int NT, int KP, bool PAD, bool X3, int KI, bool BWD,
-          class Body>
+          class Body, class Pro = NoPrologue>
 __device__ __forceinline__ void walk_tiles(const Groups& gr, int GM, int tpg,
                                            const Stager<NT, KP, PAD, X3, KI, BWD>& st,
                                            const float* __restrict__ ens, int64_t rows_total,
                                            int F, float* buf0, float* buf1,
-                                           const uint16_t* __restrict__ mask_in, Body&& tile) {
+                                           const uint16_t* __restrict__ mask_in, Body&& tile,
+                                           Pro pro = Pro()) {
+  constexpr bool kPro = !std::is_same<Pro, NoPrologue>::value;
   constexpr int PER = Stager<NT, KP, PAD, X3, KI, BWD>::PER;
   if (gr.first >= gr.end) return;
   const int count = ((gr.end - gr.first + gr.step - 1) / gr.step) * tpg;
@@ -402,11 +412,15 @@ __device__ __forceinline__ void walk_tiles(const Groups& gr, int GM, int tpg,
   uint32_t ma = 0, mb = 0, oa = 0, ob = 0;
   oa = sload(va, pf);
   ma = mload(pf);
-  st.store(buf0, va, oa);
+  if constexpr (!kPro) st.store(buf0, va, oa);
   if (count > 1) {
     pf.advance(GM, tpg, gr.step);
     ob = sload(vb, pf);
     mb = mload(pf);
+  }
+  if constexpr (kPro) {
+    pro();
+    st.store(buf0, va, oa);
   }
   pf.advance(GM, tpg, gr.step);  // pf: tile k+2
   __syncthreads();
@@ -576,12 +590,86 @@ __global__ __launch_bounds__(2 * H, 4) void k_deepset_fwd(const float* __restric
 // accumulators see a NaN (non-finite ens or dr) writes nothing and runs the fp32 form
 // instead, which gives the fp32 result.
 
-template <int H, int KP, int G, bool X3>
+// The dense chain's backward (k_chain<H, ., CH_B2D>, gine_chain.hip) for the rows of one
+// group, which at G = 16 is one 32-row chain tile:
+//   dt = (dh0 Wc) * 1[u > 0]  (Wc = the last H columns of W', ldw = FX + H)  ->  dr = dt Wf
+// dt goes to memory (the weight-gradient engine reads it) and dr straight into the walk's
+// s_dr, never to memory.  Same staging (clamped rows, zero past N), fragments, k order and
+// lane-half split as k_chain, so dt and dr are its bits.
+struct DsChainArgs {
+  const float* dh0;  // [N, H]
+  const float* u;    // [N, H]: the ReLU mask of the chain's forward
+  const float* w1;   // wfold: W' [H][FX + H] first
+  const float* w2;   // wfold2: Wf [H][H] first
+  float* dt;         // [N, H]
+  int FX;            // x width
+};
+template <int H>
+constexpr int ds_chain_lds_floats() { return 2 * 32 * (H + 4); }
+
+// sA, sB: two [32][H + 4] tiles.  Ends without a barrier: the caller's next one orders the
+// s_dr writes before the walk's reads.
+template <int H>
+__device__ __forceinline__ void ds_chain_tile(const DsChainArgs& a, int64_t N, int64_t n0,
+                                              float* sA, float* sB, float* s_dr, int wave,
+                                              int c32, int h) {
+  constexpr int NT = 2 * H, D4 = H / 4, LDA = H + 4;
+  constexpr int ITEMS = 32 * D4 / NT;  // 4
+  constexpr int RSTEP = NT / D4;       // 8
+  const int col = wave * 32 + c32;
+  const int q_me = threadIdx.x % D4, r_me = threadIdx.x / D4;
+  float4 raw[ITEMS];
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    int64_t n = n0 + r_me + i * RSTEP;
+    n = n < N ? n : N - 1;  // clamped: always issued
+    raw[i] = reinterpret_cast<const float4*>(a.dh0 + n * H)[q_me];
+  }
+  float bf[H / 2];  // stage 1's fragments, then stage 2's
+  frag_n<H>(bf, a.w1, a.FX + H, a.FX, col, h);
+  float ep[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    int64_t n = n0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    n = n < N ? n : N - 1;
+    ep[r] = a.u[n * H + col];
+  }
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    const int r = r_me + i * RSTEP;
+    *reinterpret_cast<float4*>(&sA[r * LDA + 4 * q_me]) = (n0 + r < N) ? raw[i] : f4_zero();
+  }
+  __syncthreads();
+  floatx16 acc = tile_mma<H>(sA, LDA, bf, c32, h);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+    const float v = ep[r] > 0.f ? acc[r] : 0.f;  // dt = du * 1[u > 0]
+    sB[rr * LDA + col] = v;
+    if (n0 + rr < N) a.dt[(n0 + rr) * H + col] = v;
+  }
+  frag_n<H>(bf, a.w2, H, 0, col, h);
+  __syncthreads();
+  acc = tile_mma<H>(sB, LDA, bf, c32, h);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+    // (+ 0: k_chain's bias-free second stage adds its zero bias, which turns -0 into +0)
+    // rows past N: zero whatever a zero row times a non-finite weight gave
+    s_dr[rr * H + col] = n0 + rr < N ? acc[r] + 0.f : 0.f;
+  }
+}
+
+// CHAIN (k_deepset_bwd_chain, one group per workgroup): dr is not read but made, by
+// ds_chain_tile in the walk's prologue, from `ch`
+template <int H, int KP, int G, bool X3, bool CHAIN = false>
 __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
                                             const uint16_t* __restrict__ mask,
                                             const float* __restrict__ dr,
                                             float* __restrict__ slab, int64_t N, int M, int F,
-                                            int num_groups, float* s_lds) {
+                                            int num_groups, float* s_lds,
+                                            const DsChainArgs& ch = DsChainArgs{}) {
+  static_assert(!CHAIN || G == 16, "a group is one chain tile at G = 16 only");
   constexpr int NT = 2 * H;
   constexpr int KI = ds_bwd_ki(KP);
   using I = DsBwdImg<KI>;
@@ -623,9 +711,13 @@ __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
   const int GM = G * M, tpg = tiles_per_group(G, M);
   const float* my_dr = s_dr + G * h * H + col;  // this lane: node j of its half at j*H
   int node = 0, rem = M;
-  walk_tiles<true, true>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask,
-             [&](const Cursor& c, const float* buf, uint32_t bits) {
-    if (c.t == 0) {  // dr of this group, this wave's columns (read by this wave only)
+  auto tile = [&](const Cursor& c, const float* buf, uint32_t bits) {
+    if constexpr (CHAIN) {
+      if (c.t == 0) {  // (s_dr: the prologue's)
+        node = 0;
+        rem = M;
+      }
+    } else if (c.t == 0) {  // dr of this group, this wave's columns (read by this wave only)
       const int64_t node0 = (int64_t)c.g * 2 * G;
       // all loads in flight before the first LDS store (clamped rows, zero past N)
       constexpr int kPer = 2 * G * 32 / kWave;
@@ -696,7 +788,17 @@ __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
       }
     }
     DS_MARK(3 + 0 * (int)gw[0][0]);
-  });
+  };
+  if constexpr (CHAIN) {
+    float* sA = s_dr + 2 * G * H;
+    walk_tiles<true, true>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask, tile, [&]() {
+      // one group per workgroup: blockIdx.x's (the launch has num_groups workgroups)
+      ds_chain_tile<H>(ch, N, (int64_t)gr.first * 2 * G, sA, sA + 32 * (H + 4), s_dr, wave,
+                       c32, h);
+    });
+  } else {
+    walk_tiles<true, true>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask, tile);
+  }
   if constexpr (X3) {
     bool bad = false;
 #pragma unroll
@@ -747,6 +849,27 @@ __global__ __launch_bounds__(2 * H) void k_deepset_bwd(const float* __restrict__
   __syncthreads();  // a non-finite operand: the fp32 form
 #endif
   ds_bwd_body<H, KP, G, false>(ens, mask, dr, slab, N, M, F, num_groups, s_lds);
+}
+
+// The DeepSet backward with the dense chain's backward in front of it (G = 16, one group per
+// workgroup: gridDim.x == num_groups): each workgroup makes the dr of its own 32 nodes from
+// their dh0 rows (ds_chain_tile) while the walk's first tiles are in flight, instead of a
+// chain launch writing dr for this one to read back.  No workgroup waits for another.
+template <int H, int KP>
+__global__ __launch_bounds__(2 * H) void k_deepset_bwd_chain(const float* __restrict__ ens,
+                                                             const uint16_t* __restrict__ mask,
+                                                             DsChainArgs ch,
+                                                             float* __restrict__ slab, int64_t N,
+                                                             int M, int F, int num_groups) {
+  __shared__ __attribute__((aligned(16)))
+  float s_lds[ds_bwd_lds_floats<H, KP, 16>() + ds_chain_lds_floats<H>()];
+#if GINE_DS_BWD_BF16X3
+  if (ds_bwd_body<H, KP, 16, true, true>(ens, mask, nullptr, slab, N, M, F, num_groups, s_lds,
+                                         ch))
+    return;
+  __syncthreads();  // a non-finite operand: the fp32 form (the chain tile again: same values)
+#endif
+  ds_bwd_body<H, KP, 16, false, true>(ens, mask, nullptr, slab, N, M, F, num_groups, s_lds, ch);
 }
 
 // 16 consecutive slab elements x 16 chunk groups per workgroup (many workgroups for the
@@ -948,6 +1071,63 @@ extern "C" int gine_deepset_bwd(const float* ens, const uint16_t* mask, const fl
   if (!dw1) return GINE_OK;  // slab left for gine_grad_finalize_batch
   hipLaunchKernelGGL(k_deepset_slab_reduce, dim3((unsigned)ceil_div(per, 16)), dim3(256), 0, s,
                      slab, grid, per, (int64_t)hidden * in_features, dw1, db1);
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+// The fused form's shapes: the doubly folded chain's widths, 16-node halves (a group is one
+// chain tile) and one group per workgroup (no prologue inside the walk).  Not H = 64 with 41
+// to 48 features: k_deepset_bwd<64, 48, .> spills to scratch, and so would its fused form.
+static bool bwd_chain_ok(int64_t N, int H, int F, int FX) {
+  return (H == 64 || H == 128) && F > 0 && pad_bwd(F) >= 0 && !(H == 64 && pad_bwd(F) == 48) &&
+         FX >= 1 && FX <= 64 && N > 0 &&
+         N < (int64_t(1) << 31) && nodes_per_half(N, H) == 16 &&
+         num_groups(N, H) == bwd_grid(N, H);
+}
+
+extern "C" int gine_deepset_bwd_chain_ok(int64_t num_nodes, int32_t hidden,
+                                         int32_t in_features, int32_t x_features,
+                                         int32_t* ok) {
+  if (!ok) return GINE_ERR_INVALID;
+  *ok = bwd_chain_ok(num_nodes, hidden, in_features, x_features) ? 1 : 0;
+  return GINE_OK;
+}
+
+extern "C" int gine_deepset_bwd_chain(const float* ens, const uint16_t* mask, const float* dh0,
+                                      const float* u, const float* wfold, const float* wfold2,
+                                      float* dt, float* slab, float* dw1, float* db1,
+                                      int64_t num_nodes, int32_t members, int32_t in_features,
+                                      int32_t hidden, int32_t x_features, void* stream) {
+  const int KP = pad_bwd(in_features);
+  if ((hidden != 64 && hidden != 128) || KP < 0 || in_features <= 0) return GINE_ERR_DIM;
+  if (x_features < 1 || x_features > 64) return GINE_ERR_DIM;
+  if (num_nodes <= 0 || members <= 0 || !slab) return GINE_ERR_INVALID;
+  if (!ens || !mask || !dh0 || !u || !wfold || !wfold2 || !dt) return GINE_ERR_INVALID;
+  if (num_nodes * members >= (int64_t(1) << 31)) return GINE_ERR_TOO_LARGE;
+  if (!bwd_chain_ok(num_nodes, hidden, in_features, x_features)) return GINE_ERR_INVALID;
+  const int groups = num_groups(num_nodes, hidden);
+  const int64_t per = (int64_t)hidden * in_features + hidden;
+  const DsChainArgs ch{dh0, u, wfold, wfold2, dt, x_features};
+  hipStream_t s = as_stream(stream);
+#define LAUNCH_BWD_C(H_, KP_)                                                                 \
+  hipLaunchKernelGGL((k_deepset_bwd_chain<H_, KP_>), dim3(groups), dim3(2 * H_), 0, s, ens,   \
+                     mask, ch, slab, num_nodes, members, in_features, groups)
+  if (hidden == 64) {
+    switch (KP) {  // (48: not eligible)
+      case 16: LAUNCH_BWD_C(64, 16); break;
+      case 32: LAUNCH_BWD_C(64, 32); break;
+      case 36: LAUNCH_BWD_C(64, 36); break;
+      case 40: LAUNCH_BWD_C(64, 40); break;
+      default: LAUNCH_BWD_C(64, 64); break;
+    }
+  } else {
+    DS_BWD_KP(128, KP, LAUNCH_BWD_C);
+  }
+#undef LAUNCH_BWD_C
+  GINE_LAUNCH_STATUS();
+  if (!dw1) return GINE_OK;  // slab left for gine_grad_finalize_batch
+  hipLaunchKernelGGL(k_deepset_slab_reduce, dim3((unsigned)ceil_div(per, 16)), dim3(256), 0, s,
+                     slab, groups, per, (int64_t)hidden * in_features, dw1, db1);
   GINE_LAUNCH_STATUS();
   return GINE_OK;
 }

@@ -223,6 +223,8 @@ _SIGNATURES = {
     "gine_deepset_bwd_num_partials": [_i64, _i32, ctypes.POINTER(_i32)],
     "gine_deepset_bwd": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                          _i64, _i32, _i32, _i32, _c_void_p],
+    "gine_deepset_bwd_chain_ok": [_i64, _i32, _i32, _i32, ctypes.POINTER(_i32)],
+    "gine_deepset_bwd_chain": [_c_void_p] * 10 + [_i64, _i32, _i32, _i32, _i32, _c_void_p],
     "gine_head_fwd": [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p],
     "gine_head_fwd_count": [_c_void_p] * 5 + [_i64, _i32, _i32] + [_c_void_p] * 3,
     "gine_head_bwd_slab_floats": [_i64, _i32, _i32, ctypes.POINTER(_size)],

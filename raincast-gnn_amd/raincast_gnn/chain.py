@@ -23,7 +23,7 @@ import ctypes
 
 import torch
 
-from . import _lib, gradbuf
+from . import _lib, deepset, gradbuf
 from .gradbuf import grad_out
 
 HIDDEN = (64, 128)
@@ -179,6 +179,113 @@ class _ChainFolded2Fn(torch.autograd.Function):
                       P(gfold), P(g2fold), N, D, F, stream)
             unfold(stream)
         return (dr, None, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], None, None)
+
+
+class _ChainFolded2FnEnc(_ChainFolded2Fn):
+    """:class:`_ChainFolded2Fn` for the shapes where the encoder's backward is one launch
+    (``options.ENC_BWD_FUSED``, gine_deepset_bwd_chain).  Same forward and saved tensors; the
+    backward makes dt and, on chip, dr inside the DeepSet backward launch, so it also
+    produces phi[0]'s gradients: they reach the DeepSet node (``deepset._PhiSumEncFn``, which
+    returns them to autograd) through ``link`` and r gets no gradient tensor.  The
+    weight-gradient engine, which needs dt, follows the fused launch.  Same bits as the two
+    Functions."""
+
+    @staticmethod
+    def forward(ctx, r, x, wp2, bp2, wr0, br0, wr1, br1, wdr, bdr, members, wfold, link):
+        ctx.link = link
+        return _ChainFolded2Fn.forward(ctx, r, x, wp2, bp2, wr0, br0, wr1, br1, wdr, bdr,
+                                       members, wfold)
+
+    @staticmethod
+    def backward(ctx, dh0):
+        r, x, u, wfold, wp2, bp2, wr0, wr1, br1, wdr = ctx.saved_tensors
+        link = ctx.link
+        ens, mask = link.ens, link.mask
+        N, M, Fe = ens.shape
+        D, F = r.size(1), x.size(1)
+        dev = r.device
+        n1 = 2 * D * (F + D) + D
+        wf1, wf2 = wfold[:n1], wfold[n1:]
+        dh0 = dh0.contiguous()
+        dt = torch.empty(N, D, dtype=torch.float32, device=dev)
+        floats = ctypes.c_size_t(0)
+        _lib.call("gine_chain_bwd_slab_floats", N, D, F, ctypes.byref(floats))
+        slab = torch.empty(floats.value, dtype=torch.float32, device=dev)
+        gf = torch.empty(D * (F + D) + D + D * D + D, dtype=torch.float32, device=dev)
+        gfold, g2fold = gf[:D * (F + D) + D], gf[D * (F + D) + D:]
+        p = ctx.params
+        g = [grad_out(p[0], (D, D), dev), grad_out(p[1], (D,), dev),
+             grad_out(p[2], (D, D), dev), grad_out(p[3], (D,), dev),
+             grad_out(p[4], (D, D), dev), grad_out(p[5], (D,), dev),
+             grad_out(p[6], (D, F + D), dev), grad_out(p[7], (D,), dev)]
+        parts = ctypes.c_int32(0)
+        _lib.call("gine_deepset_bwd_num_partials", N, D, ctypes.byref(parts))
+        ds_slab = torch.empty(parts.value * (D * Fe + D), dtype=torch.float32, device=dev)
+        dw = grad_out(link.params[0], (D, Fe), dev)
+        db = grad_out(link.params[1], (D,), dev)
+        P = _lib.ptr
+        stream = _lib.stream_handle(dev)
+        ds_defer = gradbuf.deferrable(dw, db)  # slab reduced in the end-of-backward batch
+        # dt (to memory, for the engine below) and dr (on chip) per 32-node group, then that
+        # group's DeepSet weight-gradient partials: one launch
+        _lib.call("gine_deepset_bwd_chain", P(ens), P(mask), P(dh0), P(u), P(wf1), P(wf2), P(dt),
+                  P(ds_slab), None if ds_defer else P(dw), None if ds_defer else P(db), N, M,
+                  Fe, D, F, stream)
+        # raw pointers only: a reference to a gradient tensor held past this function would
+        # stop autograd adopting it as param.grad (it copies a shared tensor)
+        ptrs = (P(gfold), P(wr1), P(br1), P(wdr), P(g[6]), P(g[7]), P(g[4]), P(g[5]),
+                P(g2fold), P(wp2), P(bp2), P(wr0), P(g[2]), P(g[3]), P(g[0]), P(g[1]),
+                ctx.members)
+
+        def unfold(st):
+            _lib.call("gine_chain_unfold_grads2", *ptrs, D, F, st)
+
+        if gradbuf.deferrable(*g):
+            _lib.call("gine_chain_wgrad_folded2", P(dh0), P(x), P(r), P(u), P(dt), P(slab), None,
+                      None, N, D, F, stream)
+            job = _lib.GradJob()
+            _lib.call("gine_chain_wgrad_folded2_grad_job", N, D, F, P(slab), P(gfold),
+                      P(g2fold), ctypes.byref(job))
+            gradbuf.defer(job, dev, (slab, gf, wp2, bp2, wr0, wr1, br1, wdr), post=unfold)
+        else:
+            _lib.call("gine_chain_wgrad_folded2", P(dh0), P(x), P(r), P(u), P(dt), P(slab),
+                      P(gfold), P(g2fold), N, D, F, stream)
+            unfold(stream)
+        if ds_defer:
+            job = _lib.GradJob()
+            _lib.call("gine_deepset_bwd_grad_job", N, Fe, D, P(ds_slab), P(dw), P(db),
+                      ctypes.byref(job))
+            gradbuf.defer(job, dev, (ds_slab,))
+        link.put(dw, db)
+        del dw, db
+        return (None, None, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], None, None, None)
+
+
+def encoder_fusable(ens: torch.Tensor, x: torch.Tensor, lin1) -> bool:
+    """True where :func:`encoder` applies: gradients are being recorded for phi[0] and the
+    library takes the shape (gine_deepset_bwd_chain_ok).  The callers have checked
+    ``deepset.fusable`` and :func:`fusable_dims`."""
+    if not (FOLD and torch.is_grad_enabled() and lin1.weight.requires_grad
+            and lin1.bias.requires_grad):
+        return False
+    ok = ctypes.c_int32(0)
+    _lib.call("gine_deepset_bwd_chain_ok", ens.size(0), lin1.out_features, ens.size(2),
+              x.size(1), ctypes.byref(ok))
+    return bool(ok.value)
+
+
+def encoder(ens: torch.Tensor, x: torch.Tensor, lin1, lins) -> torch.Tensor:
+    """``dim_red(cat([x, rho(phi(ens) summed over members)]))``: ``deepset.phi_sum`` with the
+    fold, then :func:`chain`, as two autograd nodes that share one backward launch
+    (gine_deepset_bwd_chain) plus the weight-gradient engine: one launch fewer than the two
+    Functions' backward.  ``lins`` = (phi[2], rho[0], rho[2], dim_red)."""
+    p2, r0, r1, dr = lins
+    link = deepset.EncLink()
+    r, wfold = deepset._PhiSumEncFn.apply(
+        ens, lin1.weight, lin1.bias,
+        tuple(t for m in (r1, dr, r0, p2) for t in (m.weight, m.bias)), link)
+    return _ChainFolded2FnEnc.apply(r, x, p2.weight, p2.bias, r0.weight, r0.bias, r1.weight,
+                                    r1.bias, dr.weight, dr.bias, ens.size(1), wfold, link)
 
 
 # False: the unfolded chain (four GEMM stages forward, s and e materialised); measured slower

@@ -95,6 +95,49 @@ class _PhiSumFn(torch.autograd.Function):
         return None, dw, db, None
 
 
+class EncLink:
+    """What the two autograd nodes of the fused encoder backward (``chain.encoder``) share:
+    the DeepSet node's operands for the chain node, whose backward launch
+    (gine_deepset_bwd_chain) also produces phi[0]'s gradients, and those gradients on their
+    way back to the DeepSet node, which returns them to autograd."""
+
+    def __init__(self):
+        self.ens = self.mask = self.params = None
+        self._grads = None
+
+    def put(self, dw, db):
+        self._grads = (dw, db)
+
+    def take(self):
+        g, self._grads = self._grads, None
+        return g
+
+
+class _PhiSumEncFn(_PhiSumFn):
+    """:class:`_PhiSumFn` in its folding form, as the DeepSet node of the fused encoder
+    backward: the chain node (``chain._ChainFolded2FnEnc``) runs the backward launch for both
+    and leaves dW1 / db1 in ``link``; this node gets no dr and only hands them on.  A dr that
+    does arrive without them (the chain node did not run) takes the DeepSet backward launch."""
+
+    @staticmethod
+    def forward(ctx, ens, weight, bias, fold, link):
+        out = _PhiSumFn.forward(ctx, ens, weight, bias, fold)
+        ctx.link = link
+        link.ens, link.mask = ctx.to_save
+        link.params = ctx.params
+        assert link.mask is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dr, *unused):
+        grads = ctx.link.take()
+        if grads is None:
+            return (*_PhiSumFn.backward(ctx, dr, *unused), None)
+        if dr is not None:
+            raise RuntimeError("r of the fused encoder has a consumer beside the chain")
+        return None, grads[0], grads[1], None, None
+
+
 def phi_sum(ens: torch.Tensor, lin1: torch.nn.Linear, fold=None):
     """``relu(lin1(ens)).sum(dim=1)`` for ens [N, M, F] on the fused kernels; with
     ``fold`` = the (rho[2], dim_red, rho[0], phi[2]) Linears, (r, wfold) for the dense chain

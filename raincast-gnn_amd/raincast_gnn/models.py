@@ -137,6 +137,9 @@ class GNN(nn.Module):
                     r = deepset.phi_sum(ens, lin1)
                     assert fused_chain.fusable(r, x, lins)
                     return fused_chain.chain(r, x, lins, ens.size(1))
+                if options.ENC_BWD_FUSED and fused_chain.encoder_fusable(ens, x, lin1):
+                    # the same two launches forward, one launch fewer backward
+                    return fused_chain.encoder(ens, x, lin1, lins)
                 # the DeepSet launch also folds the chain's weights; the chain is one launch
                 r, wfold = deepset.phi_sum(ens, lin1, fold=(rho1, self.dim_red, rho0, lin2))
                 return fused_chain.chain(r, x, lins, ens.size(1), wfold)

@@ -30,6 +30,11 @@ LAYER_BWD    True: where the backward accumulator applies and the grid fits the 
 HEAD_FOLD    True: the output head's forward (GNN.aggr + PostProcess, and the loss's
              valid-target count) runs in the last GINE layer's one-launch forward
              (gine_layer_head) where that launch applies; False: its own launch.  Same bits.
+ENC_BWD_FUSED True: where gine_deepset_bwd_chain_ok says yes (16-node halves, one group per
+             workgroup: 8,193 to 16,384 nodes at D = 128) the encoder's backward -- the dense
+             chain's dt / dr stages and the DeepSet weight gradients -- is one launch
+             (gine_deepset_bwd_chain), dr never leaving the chip; False: the pair
+             (gine_chain_bwd_folded2, gine_deepset_bwd).  Same bits.
 """
 from __future__ import annotations
 
@@ -43,3 +48,4 @@ LAYER_FWD = True
 LAYER_WIN = False
 LAYER_BWD = True
 HEAD_FOLD = True
+ENC_BWD_FUSED = True
