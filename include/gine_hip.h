@@ -59,7 +59,9 @@ extern "C" {
                                   gine_field_energy / _variogram / _area(_partials): member
                                   fields scored per graph,
                                   gine_batch_fill_permuted: a batch with permuted feature
-                                  columns written into a forward's inputs */
+                                  columns written into a forward's inputs,
+                                  gine_compare_reduce / _bootstrap / _dm: paired score
+                                  comparison (block bootstrap, Diebold-Mariano) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -924,6 +926,78 @@ int gine_field_area(const void* members, int32_t dtype, int64_t row_stride,
                     int32_t stat, double* members_out, double* obs, double* crps,
                     double* crps_fair, double* rank_lo, double* rank_hi, double* members_valid,
                     double* rows_valid, double* partials, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Paired score comparison (csrc/gine_compare.hip): two fp64 score grids a and b
+ * over the same [T days, S stations].  Element (day t, station s) of a is
+ *   a[t * a_day_stride + s * a_station_stride]
+ * (strides in elements, >= 0; b has its own; nothing is copied, so column k of a [T*S, K]
+ * result is read in place).  1 <= T < 2^31, S >= 1.  A pair is VALID when both elements are
+ * non-NaN.  An optional w (fp64, own strides, finite and >= 0) is the pair's weight, NULL = 1;
+ * w is only summed, it never multiplies a or b: it lets day sums be resampled together with
+ * their valid counts as one column.
+ *
+ * Generator (counter-based: no state, no stored indices; all arithmetic mod 2^64):
+ *   mix(seed, i): z = seed + (i + 1) * 0x9E3779B97F4A7C15
+ *                 z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *                 z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *                 return z ^ (z >> 31)
+ *   nb = ceil(T / L)                                    blocks per replicate, 1 <= L <= T
+ *   start(r, j) = ((mix(seed, r * nb + j) >> 32) * T) >> 32     r = global replicate, 64-bit
+ *   draws of replicate r: for j = 0 .. nb-1, for i = 0 .. L-1: day (start(r, j) + i) mod T,
+ *                         cut off after T draws
+ * the circular moving-block bootstrap (L = 1: the ordinary one).  The multiply-shift is biased:
+ * a day's probability differs from 1/T by at most 2^-32, a relative T / 2^32.  All stations of
+ * a replicate see the same days: spatial dependence is kept.
+ *
+ * Replicate sums (gine_compare_bootstrap): for replicate r and station s, walking the draws in
+ * order, every valid pair does  A += a, B += b, W += w (or 1),  each one fp64 add from 0, in
+ * no other order and with no fma;  diff = (A - B) / W,  skill = 1 - A / B;  IEEE results stand
+ * (W = 0 gives NaN).  Outputs [R, S] fp64 row-major, each may be NULL but not all; row i is
+ * global replicate rep_first + i, so a caller may cut a run into chunks of replicates and of
+ * stations and get the same bits.  A workgroup takes GINE_COMPARE_REP_TILE / SW replicates, SW
+ * (its station lanes) the power of two >= min(S, 64); unweighted grids of S >= 8, T <= 1,024
+ * and R >= 128 are staged in LDS instead, 8 stations a workgroup, in passes of 128 replicates
+ * (every tile edge divides GINE_COMPARE_REP_TILE).  The form does not change the bits.
+ *
+ * Marginal sums (gine_compare_reduce): station_a / _b / _n [S] over the days ascending,
+ * sequentially (valid pairs only; n their count); day_a / _b / _n [T] over a day's stations in
+ * a fixed order (lane l of a wavefront adds stations l, l + 64, ... ascending, then the 64 lane
+ * sums fold in halves), the same bits every run.  Each output may be NULL, not all.
+ *
+ * Diebold-Mariano per station (gine_compare_dm), outputs [S] fp64, each may be NULL, not all:
+ *   d_t = a - b at valid t, n = the number of valid days, dbar = (sum d_t) / n;
+ *   g_k = (sum over t with t and t+k both valid of (d_t - dbar) * (d_{t+k} - dbar)) / n,
+ *   k = 0 .. lags, every sum over t ascending, a term two subtractions, a multiply and an add;
+ *   v = g_0; for k = 1 .. lags: v += 2.0 * (1.0 - k / (lags + 1.0)) * g_k   (Bartlett);
+ *   var = v / n, stat = dbar / sqrt(var), pvalue = erfc(|stat| * 0.70710678118654752440).
+ *   n < 2, var <= 0 or a non-finite var: stat and pvalue NaN; n, dbar (NaN at n = 0) and var
+ *   are written as computed.
+ *
+ * Before any HIP call: GINE_ERR_INVALID for a NULL a or b, a negative size or stride, T < 1,
+ * S < 1, block_len outside 1..T, lags outside 0..T-1, or all outputs NULL; GINE_ERR_DIM for
+ * lags > GINE_COMPARE_MAX_LAGS; GINE_ERR_TOO_LARGE for T >= 2^31 or S > 65,535 * 64 in the
+ * bootstrap.  R = 0: GINE_OK, nothing launched.  Caller-allocated buffers, no workspace, no
+ * allocation, no host synchronisation (capturable); 64-bit offsets; no floating-point atomics.
+ * ---------------------------------------------------------------------------------- */
+#define GINE_COMPARE_MAX_LAGS 64
+#define GINE_COMPARE_REP_TILE 256
+int gine_compare_reduce(const double* a, int64_t a_day_stride, int64_t a_station_stride,
+                        const double* b, int64_t b_day_stride, int64_t b_station_stride,
+                        int64_t num_days, int64_t num_stations, double* day_a, double* day_b,
+                        double* day_n, double* station_a, double* station_b, double* station_n,
+                        void* stream);
+int gine_compare_bootstrap(const double* a, int64_t a_day_stride, int64_t a_station_stride,
+                           const double* b, int64_t b_day_stride, int64_t b_station_stride,
+                           const double* w, int64_t w_day_stride, int64_t w_station_stride,
+                           int64_t num_days, int64_t num_stations, int64_t block_len,
+                           uint64_t seed, uint64_t rep_first, int64_t num_replicates,
+                           double* sum_a, double* sum_b, double* sum_w, double* diff,
+                           double* skill, void* stream);
+int gine_compare_dm(const double* a, int64_t a_day_stride, int64_t a_station_stride,
+                    const double* b, int64_t b_day_stride, int64_t b_station_stride,
+                    int64_t num_days, int64_t num_stations, int32_t lags, double* n,
+                    double* mean_d, double* var, double* stat, double* pvalue, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Batch assembly with permuted feature columns (csrc/gine_batch.hip; the

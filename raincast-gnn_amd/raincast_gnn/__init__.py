@@ -14,10 +14,13 @@ from .ensemble import EnsembleScore, EnsembleTwScore, RawEnsemble, skill
 from .fields import AreaScore, FieldScore, MemberFields
 from .importance import (FEATURE_NAMES, FeatureImportance, PermutationPlan, fill_batch,
                          permutation_importance)
+from . import compare
+from .compare import BootstrapResult, DMResult, PairedScores
 
-__all__ = ["AreaScore", "EnsembleScore", "EnsembleTwScore", "FEATURE_NAMES", "FeatureImportance",
-           "FieldScore", "Forecast", "ForecastScore", "GINEConv", "GineGraph", "MemberFields",
-           "PermutationPlan", "Predictor", "RawEnsemble", "TwScore", "fill_batch", "get_graph",
+__all__ = ["AreaScore", "BootstrapResult", "DMResult", "EnsembleScore", "EnsembleTwScore",
+           "FEATURE_NAMES", "FeatureImportance", "FieldScore", "Forecast", "ForecastScore",
+           "GINEConv", "GineGraph", "MemberFields", "PairedScores", "PermutationPlan",
+           "Predictor", "RawEnsemble", "TwScore", "compare", "fill_batch", "get_graph",
            "graph_cache", "native_library", "permutation_importance", "pit_sample", "skill"]
 
 

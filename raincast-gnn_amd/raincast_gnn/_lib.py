@@ -32,6 +32,8 @@ ENSEMBLE_MAX_MEMBERS = 64  # gine_ensemble_*: one wavefront per row
 FIELD_F32, FIELD_F64 = 0, 1  # GINE_FIELD_F32 / GINE_FIELD_F64
 FIELD_MAX, FIELD_MEAN = 0, 1  # GINE_FIELD_MAX / GINE_FIELD_MEAN
 FIELD_ROW_TILE = 64  # GINE_FIELD_ROW_TILE
+COMPARE_MAX_LAGS = 64  # GINE_COMPARE_MAX_LAGS
+COMPARE_REP_TILE = 256  # GINE_COMPARE_REP_TILE
 BATCH_MAX_FEATURES = 64  # gine_batch_fill_permuted: the bits of col_mask
 
 _c_void_p = ctypes.c_void_p
@@ -209,6 +211,13 @@ _SIGNATURES = {
                              _c_void_p, _i64, _f64] + [_c_void_p] * 6,
     "gine_field_area": [_c_void_p, _i32, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64,
                         _c_void_p, _i64, _i32] + [_c_void_p] * 10,
+    "gine_compare_reduce": [_c_void_p, _i64, _i64, _c_void_p, _i64, _i64, _i64, _i64]
+                           + [_c_void_p] * 7,
+    "gine_compare_bootstrap": [_c_void_p, _i64, _i64] * 3 + [_i64, _i64, _i64, ctypes.c_uint64,
+                                                              ctypes.c_uint64, _i64]
+                              + [_c_void_p] * 6,
+    "gine_compare_dm": [_c_void_p, _i64, _i64, _c_void_p, _i64, _i64, _i64, _i64, _i32]
+                       + [_c_void_p] * 6,
     "gine_batch_fill_permuted": [_c_void_p] * 6 + [ctypes.c_uint64, _i64, _i32, _i32, _i32, _i32,
                                                    _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "gine_linear_wgrad_num_chunks": [_i64, _i32, _i32, ctypes.POINTER(_i32)],

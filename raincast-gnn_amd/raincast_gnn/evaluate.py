@@ -163,6 +163,17 @@ def feature_importance(model: torch.nn.Module, dataset, **kw):
     return permutation_importance(model, dataset, **kw)
 
 
+def compare(model_rows: torch.Tensor, other_rows: torch.Tensor, num_stations: int, **kw):
+    """Is the difference between two sets of per-row scores more than noise?  ``[N]`` rows in
+    collated order (what :func:`predict_model` returns; ``N = days * num_stations``), e.g. the
+    ``crps_rows`` of :func:`verify` beside the raw ensemble's, or ``[N, K]`` rows with one
+    comparison per column (the twCRPS rows of ``K`` thresholds, read in place): skill and mean
+    difference overall and per station, moving-block bootstrap intervals and Diebold-Mariano
+    tests; :func:`raincast_gnn.compare.compare` with its keywords."""
+    from .compare import compare as paired
+    return paired(model_rows, other_rows, num_stations, **kw)
+
+
 @dataclass
 class TwVerification:
     """What :func:`verify_tw` returns, per threshold: the model's and the raw ensemble's mean
