@@ -417,8 +417,12 @@ int gine_mp_fwd_mlp1(const float* x, const int32_t* in_rowptr, const int32_t* in
  *     ATen's do.  partials may be NULL.
  *   gine_mlp_fwd2_bn: gine_bn_fwd_finalize (from bn_acc) + gine_mlp_fwd2 in one launch;
  *     writes bn_save, the running statistics and num_batches_tracked as the finalize does.
- * The statistics agree with the partials path to ~1e-15 relative (sums are rounded to
- * 2^-64 per workgroup), so bn_save can differ from it in the last fp32 bit. */
+ * Each workgroup sum is rounded to 2^-64, absolutely: with G workgroups the mean is within
+ * G 2^-65 / N of the partials path's and bn_save can differ from it in the last fp32 bit
+ * (~1e-15 relative for activations of order 1).  A column whose sums are themselves of order
+ * 2^-64 (|a1| ~ 1e-20 and below) loses them: measured on the 1e-30 column of
+ * tests/test_gpu_bn_stats.py, mean = 0 here against 5e-8 relative on the partials path, both
+ * inside the bounds of tests/bn_cases.py. */
 int gine_bn_acc_words(int32_t channels, int64_t* words);
 /* Index (int64 words into bn_acc) of the grid-barrier failure count: gine_mp_fwd_layer adds 1
  * there for every workgroup whose grid barrier timed out (~2 s: the grid was not resident at
