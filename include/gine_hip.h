@@ -613,7 +613,11 @@ int gine_mlp_bwd1_wgrad(const float* dy, const float* y, const uint8_t* mask, co
  * (g < 8) the sub-tickets of a two-level ticket, one per 128-byte line; every ticket word
  * must start at 0 and is left at 0) and updates param / exp_avg / exp_avg_sq in place with torch.optim.AdamW's
  * default (amsgrad=False) formulation.  One launch, graph-safe; the four buffers must be
- * 16-byte aligned (float4 accesses).
+ * 16-byte aligned (float4 accesses).  Every scalar is formed from the fp32 arguments
+ * (1.0f - beta in fp32, the bias corrections in double from the fp32 betas; gine_optim.hip's
+ * header and DESIGN.md 6d give the exact sequence), not from torch's Python doubles: at the
+ * defaults exp_avg_sq is 1.29e-5 relative below torch's, exp_avg's weight 2.2e-7 above.  The
+ * count is fp32 and stays at 2^24 once it is there (the update is still applied).
  * ---------------------------------------------------------------------------------- */
 int gine_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                     float* step, int64_t n, float lr, float beta1, float beta2, float eps,

@@ -2,13 +2,29 @@
 // training step, train.py:67-69: zero_grad / backward / AdamW.step, lr from params.json).
 //
 // torch.optim.AdamW (amsgrad=False, maximize=False) per element, default (non-capturable)
-// formulation, with the scalar bias corrections computed in double and applied in fp32 the
-// way torch applies Python scalars to fp32 tensors:
+// formulation:
 //   step += 1
 //   p  *= 1 - lr*wd
 //   m   = m + (1-b1)*(g - m)                 (lerp, weight < 0.5 branch)
 //   v   = v*b2 + (1-b2)*g*g
 //   p  += -(lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// The arithmetic below is the definition (tests/optim_oracle.py restates it and
+// tests/test_gpu_optim_rows.py holds both kernels to it bit for bit).  lr, b1, b2, eps and wd
+// arrive as fp32 and every scalar is formed from those fp32 values:
+//   decay = (float)(1 - (double)lr (double)wd)          w1 = 1.0f - b1   (fp32 subtraction)
+//   nss   = (float)(-((double)lr / (1 - (double)b1^t))) w2 = 1.0f - b2   (fp32 subtraction)
+//   bc2   = (float)sqrt(1 - (double)b2^t)               t  = step[0] + 1.0f, then widened
+// and per element, one fp32 rounding per operation (-ffp-contract=off, IEEE divide and sqrt):
+//   p = p*decay;  m = m + w1*(g - m);  v = v*b2;  v = v + (w2*g)*g;
+//   p = p + nss*(m / (sqrtf(v)/bc2 + eps))
+// This is NOT how torch applies its Python scalars: torch forms 1 - beta, the bias corrections
+// and the step size from the Python doubles and rounds once.  At the defaults w1 is
+// 0.100000024 against torch's 0.1f (+2.2e-7 relative), w2 0.00099998713 against 0.001f
+// (-1.29e-5), bc2 at t = 1 -6.4e-6, nss at t = 1 -1.9e-7; decay is the same.  The kernel's
+// choice is the self-consistent one (w2 = 1 - b2 exactly, so a constant gradient keeps
+// v / (1 - b2^t) at g*g); torch's values would need double-precision arguments.  step[0] is an
+// fp32 count: from 2^24 on it no longer advances (2^24 + 1.0f == 2^24) and t stays 2^24,
+// where both bias corrections have long been exactly 1.
 // The step counter lives on the device, so the update is legal inside a captured HIP graph
 // and replays correctly: every workgroup uses step[0] + 1, and the workgroup that finishes
 // last stores the bump -- one launch per optimizer step.  "Last" is found by a two-level

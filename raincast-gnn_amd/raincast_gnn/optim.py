@@ -108,7 +108,8 @@ class FlatAdamW:
             float(weight_decay)
         # every parameter starts on a 256-byte boundary (the kernels' weight fragment loads
         # use 16-byte vectors when a weight is aligned); the gaps stay zero in all four flat
-        # buffers, which AdamW leaves at zero
+        # buffers, which AdamW leaves at zero while eps > 0 (eps = 0 turns a gap's 0 / 0 into
+        # NaN, as torch's AdamW does to a parameter with a zero gradient: DESIGN.md 6d)
         self._offsets = []
         off = 0
         for p in self.params:
