@@ -61,7 +61,9 @@ extern "C" {
                                   gine_batch_fill_permuted: a batch with permuted feature
                                   columns written into a forward's inputs,
                                   gine_compare_reduce / _bootstrap / _dm: paired score
-                                  comparison (block bootstrap, Diebold-Mariano) */
+                                  comparison (block bootstrap, Diebold-Mariano),
+                                  gine_reliability_counts / _fit / _resample: reliability
+                                  diagrams (CORP curves, consistency bands, MCB / DSC / UNC) */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -1006,6 +1008,89 @@ int gine_compare_dm(const double* a, int64_t a_day_stride, int64_t a_station_str
                     const double* b, int64_t b_day_stride, int64_t b_station_stride,
                     int64_t num_days, int64_t num_stations, int32_t lags, double* n,
                     double* mean_d, double* var, double* stat, double* pvalue, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Reliability diagrams (csrc/gine_reliability.hip): the CORP curve of
+ * Dimitriadis, Gneiting and Jordan (2021) on a probability lattice, the split of the Brier
+ * score into miscalibration, discrimination and uncertainty, and consistency resampling
+ * (Broecker and Smith 2007).
+ *
+ * Inputs: p [N, T] fp64, element (row i, column t) at p[i * p_row_stride + t * p_col_stride]
+ * (strides in elements, >= 0, nothing copied): the probability of "y exceeds x_t"; y [N] fp32,
+ * NaN = missing; x [T] fp64; q, the lattice step count, 1 <= q <= GINE_RELIABILITY_MAX_LEVELS,
+ * levels k = 0 .. q, K = q + 1; N < 2^30, T <= 65,535.
+ *
+ * Cells: (i, t) is VALID when y_i and x_t are not NaN and 0 <= p <= 1 (NaN and out-of-range
+ * p are invalid, not an error).  Its event is o = (double)y_i > x_t (the comparison of
+ * gine_ensemble_score), its level k = (int)rint(p * q): one fp64 multiply, round half to even.
+ * The level's value is v_k = (double)k / (double)q.
+ *
+ * Counts (gine_reliability_counts), per column: n_k valid cells and e_k events among them at
+ * level k, [T, K] int32 (zeroed by the call); level [T, N] int16, -1 at an invalid cell.
+ * Integers: any traversal gives the same values.  n = sum n_k, E = sum e_k.
+ *
+ * Fit (gine_reliability_fit), per column: pool-adjacent-violators over the non-empty levels
+ * ascending with a stack of blocks (E_b, N_b): push (e_k, n_k); while the block below the top
+ * has a mean >= the top's, decided exactly in int64 as E_prev * N_top >= E_top * N_prev, merge
+ * the two.  Block means end strictly increasing.  cal [T, K]: (double)E_b / (double)N_b of the
+ * level's block, NaN at an empty level; block_id [T, K] (-1 at an empty level); block_e,
+ * block_n [T, K]: entry b < num_blocks[t] is block b, the rest 0; a2 [T] int64; stats [T, 8]
+ * fp64 = n, E, S, S_cal, UNC, MCB, DSC, AUC.  Every fp64 operation is rounded once, there is no
+ * fma, sums start at +0:
+ *   S     = (sum over non-empty k ascending of [ (double)(n_k - e_k) * (v*v)
+ *                                                + (double)e_k * ((1-v)*(1-v)) ]) / (double)n
+ *           (each bracket is formed, then added): the Brier score of the lattice forecast,
+ *           within 1/q of the Brier score of p itself;
+ *   S_cal = (sum over blocks ascending of (double)E_b * ((double)(N_b - E_b) / (double)N_b))
+ *           / (double)n;
+ *   UNC   = (double)E * ((double)(n - E) / (double)n) / (double)n;
+ *   MCB   = S - S_cal;   DSC = UNC - S_cal;
+ *   AUC   = (double)A2 / ((2.0 * (double)E) * (double)(n - E)),  A2 = sum_k e_k * (2 * C_k +
+ *           (n_k - e_k)) in int64, C_k the non-events at the levels below k (Mann-Whitney, ties
+ *           counted half).
+ * IEEE results stand: n = 0 gives NaN everywhere, E = 0 or E = n NaN for AUC.  Each output may
+ * be NULL, not all.
+ *
+ * Resampling (gine_reliability_resample): with mix(seed, i) of gine_compare_bootstrap above,
+ *   U(r, i) = mix(seed, r * N + i) >> 11      r = global replicate index, all mod 2^64,
+ * the synthetic event of cell (i, t) at level k is  U < (uint64)floor(v_k * 2^53)  (v = 0 never
+ * fires, v = 1 always).  All columns share U, so the synthetic events of falling exceedance
+ * probabilities are nested as real ones are, and column subsets and replicate chunks give the
+ * same bits.  Per (r, t): e*_k over the valid cells, n_k unchanged, the same fit.  Row i of
+ * the outputs is replicate rep_first + i: cal_rep [R, T, K] fp64 (NaN at empty levels),
+ * stats_rep [R, T, 3] fp64 = S*, S*_cal, MCB* by the formulas above with e*, e_rep [R, T, K]
+ * int32; each may be NULL, not all.  level and n_k are those gine_reliability_counts wrote (a
+ * level outside 0 .. q counts as invalid).  A workgroup takes
+ * GINE_RELIABILITY_REPS_PER_BLOCK replicate and as many columns as fit in half a CU's LDS.
+ * traversal: GINE_RELIABILITY_ATOMIC counts with one LDS integer add per synthetic event,
+ * GINE_RELIABILITY_BALLOT (K <= 64 only) per level with a wavefront ballot and popcount,
+ * GINE_RELIABILITY_AUTO takes the faster of the two as measured (the atomic form
+ * at every K).  The traversal does not change the bits.
+ *
+ * Before any HIP call: GINE_ERR_INVALID for q outside 1 .. GINE_RELIABILITY_MAX_LEVELS, a
+ * negative size or stride, a NULL operand that the sizes need, all outputs NULL, an unknown
+ * traversal or the ballot form at K > 64; GINE_ERR_TOO_LARGE for N >= 2^30, T > 65,535 or
+ * R >= 2^31.  N = 0: the counts are zeroed, nothing else is launched; T = 0 or R = 0:
+ * GINE_OK, nothing launched.  Caller-allocated buffers, no workspace, no allocation, no host
+ * synchronisation (capturable); no floating-point atomics.
+ * ---------------------------------------------------------------------------------- */
+#define GINE_RELIABILITY_MAX_LEVELS 4096
+#define GINE_RELIABILITY_REPS_PER_BLOCK 1
+#define GINE_RELIABILITY_AUTO 0
+#define GINE_RELIABILITY_ATOMIC 1
+#define GINE_RELIABILITY_BALLOT 2
+int gine_reliability_counts(const double* p, int64_t p_row_stride, int64_t p_col_stride,
+                            const float* y, const double* x, int64_t num_rows,
+                            int32_t num_thresholds, int32_t q, int32_t* n_k, int32_t* e_k,
+                            int16_t* level, void* stream);
+int gine_reliability_fit(const int32_t* n_k, const int32_t* e_k, int32_t num_thresholds,
+                         int32_t q, double* cal, int32_t* block_id, int32_t* block_e,
+                         int32_t* block_n, int32_t* num_blocks, int64_t* a2, double* stats,
+                         void* stream);
+int gine_reliability_resample(const int16_t* level, const int32_t* n_k, int64_t num_rows,
+                              int32_t num_thresholds, int32_t q, uint64_t seed,
+                              uint64_t rep_first, int64_t num_replicates, int32_t traversal,
+                              double* cal_rep, double* stats_rep, int32_t* e_rep, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Batch assembly with permuted feature columns (csrc/gine_batch.hip; the

@@ -16,12 +16,15 @@ from .importance import (FEATURE_NAMES, FeatureImportance, PermutationPlan, fill
                          permutation_importance)
 from . import compare
 from .compare import BootstrapResult, DMResult, PairedScores
+from . import reliability
+from .reliability import Reliability, ReliabilityBands, ReliabilityFit
 
 __all__ = ["AreaScore", "BootstrapResult", "DMResult", "EnsembleScore", "EnsembleTwScore",
            "FEATURE_NAMES", "FeatureImportance", "FieldScore", "Forecast", "ForecastScore",
            "GINEConv", "GineGraph", "MemberFields", "PairedScores", "PermutationPlan",
-           "Predictor", "RawEnsemble", "TwScore", "compare", "fill_batch", "get_graph",
-           "graph_cache", "native_library", "permutation_importance", "pit_sample", "skill"]
+           "Predictor", "RawEnsemble", "Reliability", "ReliabilityBands", "ReliabilityFit",
+           "TwScore", "compare", "fill_batch", "get_graph", "graph_cache", "native_library",
+           "permutation_importance", "pit_sample", "reliability", "skill"]
 
 
 def native_library():

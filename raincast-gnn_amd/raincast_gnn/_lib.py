@@ -34,6 +34,10 @@ FIELD_MAX, FIELD_MEAN = 0, 1  # GINE_FIELD_MAX / GINE_FIELD_MEAN
 FIELD_ROW_TILE = 64  # GINE_FIELD_ROW_TILE
 COMPARE_MAX_LAGS = 64  # GINE_COMPARE_MAX_LAGS
 COMPARE_REP_TILE = 256  # GINE_COMPARE_REP_TILE
+RELIABILITY_MAX_LEVELS = 4096  # GINE_RELIABILITY_MAX_LEVELS
+RELIABILITY_REPS_PER_BLOCK = 1  # GINE_RELIABILITY_REPS_PER_BLOCK
+RELIABILITY_AUTO, RELIABILITY_ATOMIC, RELIABILITY_BALLOT = 0, 1, 2  # GINE_RELIABILITY_*
+RELIABILITY_BALLOT_MAX_LEVELS = 64  # the ballot traversal: one lane per level
 BATCH_MAX_FEATURES = 64  # gine_batch_fill_permuted: the bits of col_mask
 
 _c_void_p = ctypes.c_void_p
@@ -218,6 +222,11 @@ _SIGNATURES = {
                               + [_c_void_p] * 6,
     "gine_compare_dm": [_c_void_p, _i64, _i64, _c_void_p, _i64, _i64, _i64, _i64, _i32]
                        + [_c_void_p] * 6,
+    "gine_reliability_counts": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32]
+                               + [_c_void_p] * 4,
+    "gine_reliability_fit": [_c_void_p, _c_void_p, _i32, _i32] + [_c_void_p] * 8,
+    "gine_reliability_resample": [_c_void_p, _c_void_p, _i64, _i32, _i32, ctypes.c_uint64,
+                                  ctypes.c_uint64, _i64, _i32] + [_c_void_p] * 4,
     "gine_batch_fill_permuted": [_c_void_p] * 6 + [ctypes.c_uint64, _i64, _i32, _i32, _i32, _i32,
                                                    _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "gine_linear_wgrad_num_chunks": [_i64, _i32, _i32, ctypes.POINTER(_i32)],

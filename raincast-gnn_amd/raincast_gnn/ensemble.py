@@ -178,6 +178,17 @@ class RawEnsemble:
             return self._launch_score(None, x, None)
         return self._score_torch(None, x)[1]
 
+    def reliability(self, y: torch.Tensor, thresholds, unit: str = "model",
+                    levels: int | None = None):
+        """The ensemble's exceedance frequencies at ``thresholds`` beside the targets ``y [N]``
+        as a :class:`raincast_gnn.reliability.Reliability`.  ``levels`` defaults to the number
+        of members ``M``: without NaN members every frequency ``k / M`` is on that lattice
+        exactly.  A row without members (NaN frequency) is invalid."""
+        from .reliability import Reliability
+        q = self.members.size(1) if levels is None else levels
+        return Reliability(self.exceedance(thresholds, unit), y,
+                           _thresholds(thresholds, unit, self.device), levels=q)
+
     def rank_histogram(self, score: EnsembleScore, generator=None) -> torch.Tensor:
         """Counts ``[M + 1]`` of the verification rank over the valid rows (Talagrand diagram).
         A target tied with members takes a rank drawn uniformly from ``rank_lo..rank_hi``, the

@@ -204,3 +204,39 @@ def verify_tw(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor
     m = torch.where(both, ft.rows, zero).sum(0) / count
     e = torch.where(both, er, zero).sum(0) / count
     return TwVerification(m, e, skill(m, e), count, ft.thresholds)
+
+
+@dataclass
+class ReliabilityVerification:
+    """What :func:`verify_reliability` returns for one forecast: the
+    :class:`raincast_gnn.reliability.Reliability`, its fit and, with ``replicates > 0``, its
+    consistency bands (else None)."""
+    reliability: object
+    fit: object
+    bands: object
+
+
+def verify_reliability(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor,
+                       thresholds, raw=None, unit: str = "mm", levels: int = 1000,
+                       raw_levels: int | None = None, replicates: int = 1000, seed: int = 0,
+                       level: float = 0.9, max_bytes: int = 256 << 20):
+    """Reliability of the predictions' exceedance probabilities at ``thresholds`` (``unit``:
+    millimetres by default): the CORP curve, the Brier score split into MCB, DSC and UNC, the
+    AUC, and with ``replicates > 0`` the consistency band at ``level`` and the Monte-Carlo
+    p-value (:mod:`raincast_gnn.reliability`).  With ``raw`` (a
+    :class:`raincast_gnn.ensemble.RawEnsemble` of the same rows) returns ``(model, ensemble)``,
+    the ensemble's frequencies on a lattice of ``raw_levels`` steps (its member count by
+    default)."""
+    from .forecast import Forecast
+
+    def one(rel):
+        bands = rel.resample(replicates, seed=seed, level=level,
+                             max_bytes=max_bytes) if replicates > 0 else None
+        return ReliabilityVerification(rel, rel.fit(), bands)
+
+    mine = one(Forecast.from_model(model, preds).reliability(targets, thresholds, unit=unit,
+                                                             levels=levels))
+    if raw is None:
+        return mine
+    return mine, one(raw.reliability(targets.to(raw.device), thresholds, unit=unit,
+                                     levels=raw_levels))

@@ -229,6 +229,15 @@ class Forecast:
             return self._twcrps_hip(y, x, rows)
         return self._twcrps_cpu(y, x, rows)
 
+    def reliability(self, y: torch.Tensor, thresholds, unit: str = "model", levels: int = 1000):
+        """The exceedance probabilities at ``thresholds`` (``unit``: theirs) beside the targets
+        ``y [N]`` (model space, NaN = missing) as a :class:`raincast_gnn.reliability.Reliability`
+        on a lattice of ``levels`` steps: CORP reliability curve, MCB / DSC / UNC, consistency
+        bands."""
+        from .reliability import Reliability
+        return Reliability(self.exceedance(thresholds, unit), y, self._thresholds(thresholds, unit),
+                           levels=levels)
+
     def ecc(self, raw, levels: str = "uniform", unit: str = "model") -> torch.Tensor:
         """Ensemble copula coupling (ECC-Q): the post-processed members ``[N, M]``.  Member
         ``i`` of ``raw`` (a :class:`raincast_gnn.ensemble.RawEnsemble`) is replaced by this
