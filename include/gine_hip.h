@@ -795,6 +795,51 @@ int gine_forecast_score(const float* pred, const float* y, int64_t num_nodes, in
                         double* valid, double* partials, uint32_t* ticket, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The linear pool of num_members checkpoint forecasts (additive in ABI 10):
+ *   Fbar(x) = sum_m w_m F_m(x),  sfbar(x) = sum_m w_m sf_m(x)  (members in index order),
+ * F_m the distribution above of member m's row of preds [num_members, N, K] fp32 (contiguous;
+ * one kind, u, xi, c for all members).  weights: num_members fp64 on the device, > 0, summing
+ * to 1 (normalised by the caller).  1 <= num_members <= 32, negative sizes and the domain
+ * errors of gine_forecast_* are GINE_ERR_INVALID before any HIP call; num_nodes = 0 is
+ * GINE_OK and launches nothing; more than 2^31 - 1 rows or 2^24 points GINE_ERR_TOO_LARGE.
+ * One launch each, no allocation, no host synchronisation.  A pool of one member of weight
+ * 1, or of 2^k copies of one member at equal weights, returns the bits of gine_forecast_*.
+ * gine_pool_prob: out[n, t] = Fbar(x[t]); with GINE_FORECAST_UPPER sfbar(x[t]).
+ * gine_pool_quantile: out[n, j] = inf{x : Fbar(x) >= level}: the edge levels as
+ *   gine_forecast_quantile; c for a level up to sum_m w_m P_c,m (GINE_FORECAST_UPPER: for
+ *   s >= sum_m w_m S_c,m); the members' common quantile where they agree; otherwise the upper
+ *   end of a bracket of two adjacent doubles found by a safeguarded Newton / bisection
+ *   between the members' quantiles (at most 89 evaluations of the pool; the upper form
+ *   solves sfbar(x) = s).  level_row_stride 0: level[j] for every row; otherwise row n reads
+ *   level[n * level_row_stride + j] (level_row_stride >= num_levels).
+ * gine_pool_score: the scores of targets y [N] fp32 (NaN = missing) in one launch, one
+ *   workgroup per row: crps_rows = member_crps_rows - diversity_rows, member_crps_rows =
+ *   sum_m w_m crps_m(y) (the closed forms of gine_forecast_score), diversity_rows = V =
+ *   int sum_m w_m (F_m - Fbar)^2 dx >= 0, which depends on no target (written for NaN targets
+ *   too; exactly 0 for equal members) and is integrated by 16-point Gauss-Legendre panels
+ *   between the sorted breakpoints c, u_m, mu_m + k sigma_m (k = 0, +-1, 2, 3, 5, 8) and, for
+ *   the two MIXED kinds, one 32-point Gauss-Jacobi panel over [max u_m, inf): jacobi_nodes /
+ *   jacobi_weights [32] are that rule's on [0, 1] for the weight w^(2/xi - 2) (device
+ *   pointers; unused and may be NULL for the other kinds).  pit_lo / pit_hi, brier, valid,
+ *   ticket as gine_forecast_score, from Fbar and sfbar.  Every row output may be NULL.
+ *   partials: gine_pool_score_partials() doubles.
+ * ---------------------------------------------------------------------------------- */
+int gine_pool_prob(const float* preds, int32_t num_members, int64_t num_nodes, int32_t kind,
+                   double u, double xi, double c, const double* weights, const double* x,
+                   int32_t num_x, int32_t flags, double* out, void* stream);
+int gine_pool_quantile(const float* preds, int32_t num_members, int64_t num_nodes, int32_t kind,
+                       double u, double xi, double c, const double* weights,
+                       const double* level, int32_t num_levels, int64_t level_row_stride,
+                       int32_t flags, double* out, void* stream);
+int gine_pool_score_partials(int64_t num_nodes, int32_t num_x, size_t* count);
+int gine_pool_score(const float* preds, const float* y, int32_t num_members, int64_t num_nodes,
+                    int32_t kind, double u, double xi, double c, const double* weights,
+                    const double* x, int32_t num_x, const double* jacobi_nodes,
+                    const double* jacobi_weights, double* crps_rows, double* member_crps_rows,
+                    double* diversity_rows, double* pit_lo, double* pit_hi, double* brier,
+                    double* valid, double* partials, uint32_t* ticket, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The raw ensemble beside that distribution: M <= 64 members per row (one wavefront a row),
  * read in place from a strided fp32 view: member i of row n is
  *   x = shift + scale * (double)members[n * row_stride + i * member_stride]

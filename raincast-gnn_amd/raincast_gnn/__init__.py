@@ -18,13 +18,16 @@ from . import compare
 from .compare import BootstrapResult, DMResult, PairedScores
 from . import reliability
 from .reliability import Reliability, ReliabilityBands, ReliabilityFit
+from . import pool
+from .pool import ForecastPool, PoolScore
 
 __all__ = ["AreaScore", "BootstrapResult", "DMResult", "EnsembleScore", "EnsembleTwScore",
-           "FEATURE_NAMES", "FeatureImportance", "FieldScore", "Forecast", "ForecastScore",
+           "FEATURE_NAMES", "FeatureImportance", "FieldScore", "Forecast", "ForecastPool",
+           "ForecastScore",
            "GINEConv", "GineGraph", "MemberFields", "PairedScores", "PermutationPlan",
-           "Predictor", "RawEnsemble", "Reliability", "ReliabilityBands", "ReliabilityFit",
+           "PoolScore", "Predictor", "RawEnsemble", "Reliability", "ReliabilityBands", "ReliabilityFit",
            "TwScore", "compare", "fill_batch", "get_graph", "graph_cache", "native_library",
-           "permutation_importance", "pit_sample", "reliability", "skill"]
+           "permutation_importance", "pit_sample", "pool", "reliability", "skill"]
 
 
 def native_library():

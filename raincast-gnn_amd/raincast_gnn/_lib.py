@@ -193,6 +193,13 @@ _SIGNATURES = {
     "gine_forecast_score_partials": [_i64, _i32, ctypes.POINTER(_size)],
     "gine_forecast_score": [_c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i32]
                            + [_c_void_p] * 8,
+    "gine_pool_prob": [_c_void_p, _i32, _i64, _i32, _f64, _f64, _f64, _c_void_p, _c_void_p, _i32,
+                       _i32, _c_void_p, _c_void_p],
+    "gine_pool_quantile": [_c_void_p, _i32, _i64, _i32, _f64, _f64, _f64, _c_void_p, _c_void_p,
+                           _i32, _i64, _i32, _c_void_p, _c_void_p],
+    "gine_pool_score_partials": [_i64, _i32, ctypes.POINTER(_size)],
+    "gine_pool_score": [_c_void_p, _c_void_p, _i32, _i64, _i32, _f64, _f64, _f64, _c_void_p,
+                        _c_void_p, _i32] + [_c_void_p] * 12,
     "gine_ensemble_score": [_c_void_p, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64, _c_void_p,
                             _i32] + [_c_void_p] * 7,
     "gine_ensemble_ecc": [_c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i64, _i64, _i32,

@@ -39,14 +39,17 @@ def predict_model(model: torch.nn.Module, batches: Iterable, device,
 
 
 def predict_ensemble(make_model, checkpoints, batches, device,
-                     fused: bool = False) -> torch.Tensor:
+                     fused: bool = False, stack: bool = False) -> torch.Tensor:
     """eval.py:178-212: one model per checkpoint (state_dict path or dict), predictions
     averaged over checkpoints.  ``batches`` is re-iterated per checkpoint.
     ``fused``: one model and its ``Predictor`` for all checkpoints, each loaded into the model
     in place (``load_state_dict`` copies into the parameters' storage, which the captured
     forward reads).  The batches are moved to the device once, so every checkpoint sees the
     same tensors: per distinct edge list (up to the Predictor's ``max_captures``) one eager
-    call and one capture, then a replay per further checkpoint."""
+    call and one capture, then a replay per further checkpoint.
+    ``stack``: the checkpoints' predictions as they are, ``[M, N, K]``, for
+    :class:`raincast_gnn.pool.ForecastPool`; the mean over parameter rows is left to the
+    caller (``.mean(0)`` is the default return)."""
     batches = [b.to(device) for b in batches] if fused else list(batches)
     preds = []
     model = None
@@ -57,6 +60,8 @@ def predict_ensemble(make_model, checkpoints, batches, device,
             else ck
         model.load_state_dict(state)
         preds.append(predict_model(model, batches, device, fused))
+    if stack:
+        return torch.stack(preds, dim=0)
     if len(preds) == 1:
         return preds[0]
     return torch.stack(preds, dim=0).mean(dim=0)
@@ -75,6 +80,39 @@ def verify(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor, t
     On a HIP device one launch; returns a :class:`raincast_gnn.forecast.ForecastScore`."""
     from .forecast import Forecast
     return Forecast.from_model(model, preds).score(targets, thresholds, unit=unit)
+
+
+@dataclass
+class PoolVerification:
+    """What :func:`verify_pool` returns.  ``pool``: the :class:`raincast_gnn.pool.PoolScore` of
+    the linear pool; ``average``: the :class:`raincast_gnn.forecast.ForecastScore` of the
+    parameter average (what :func:`verify` gives for ``stacked.mean(0)``); the means over the
+    valid rows obey ``pool_crps = member_crps - diversity``."""
+    pool: object
+    average: object
+    pool_crps: torch.Tensor
+    average_crps: torch.Tensor
+    member_crps: torch.Tensor
+    diversity: torch.Tensor
+
+
+def verify_pool(model: torch.nn.Module, stacked: torch.Tensor, targets: torch.Tensor, thresholds,
+                unit: str = "mm", weights=None) -> PoolVerification:
+    """The checkpoints' forecasts ``stacked [M, N, K]`` (``predict_ensemble(..., stack=True)``)
+    scored as their linear pool (:mod:`raincast_gnn.pool`) beside the parameter average: the
+    two scores, the mean CRPS of each, the weighted mean member CRPS and the mean diversity
+    over the rows with a target."""
+    from .forecast import Forecast
+    from .pool import ForecastPool
+    pool = ForecastPool.from_model(model, stacked, weights=weights).score(targets, thresholds,
+                                                                          unit=unit)
+    average = Forecast.from_model(model, stacked.mean(dim=0)).score(targets, thresholds,
+                                                                    unit=unit)
+    ok = ~torch.isnan(pool.crps_rows)
+    diversity = torch.where(ok, pool.diversity_rows, torch.zeros_like(pool.diversity_rows)).sum() \
+        / pool.valid[0]
+    member = torch.nansum(pool.member_crps_rows) / pool.valid[0]
+    return PoolVerification(pool, average, pool.crps, average.crps, member, diversity)
 
 
 @dataclass
