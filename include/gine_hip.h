@@ -840,6 +840,34 @@ int gine_pool_score(const float* preds, const float* y, int32_t num_members, int
                     double* valid, double* partials, uint32_t* ticket, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Pair sums for fitting the pool's weights (additive in ABI 10).  Summed over
+ * rows with a target, the pool's CRPS is c . w - 1/2 w' D w: c_m the sum of member m's
+ * closed-form CRPS, D_ml the sum of int (F_m - F_l)^2 dx.  gine_pool_pairs gives both, and
+ * the number of rows, per segment g of rows ptr[g] <= i < ptr[g + 1] (ptr [num_segments + 1]
+ * int64 on the device, ptr[0] = 0, non-decreasing, ptr[num_segments] = num_nodes; the caller
+ * validates it; empty segments are allowed), over the rows whose target is not NaN:
+ *   count [G], member_crps [G, M], distance [G, M (M - 1) / 2] with the pairs packed
+ *   (0,1), (0,2), ..., (M-2, M-1); distance may be NULL for one member.
+ * Each integral by gine_pool_score's rule for the row -- the breakpoints of all M members, empty
+ * panels skipped, 16-point Gauss-Legendre panels and for the MIXED kinds the Gauss-Jacobi panel
+ * (jacobi_nodes / jacobi_weights as gine_pool_score), the difference there from the exceedance
+ * probabilities -- every term formed as wq (F_m - F_l) (F_m - F_l): equal members give exactly
+ * 0, and swapping or permuting members permutes the results bit for bit.  No weights: nothing
+ * here depends on them.  One launch; rows are added in a fixed order per segment (64-row tiles
+ * of the segment, then the tiles), no fp64 atomics: the bits depend on M and on the segment's
+ * rows alone.  partials: gine_pool_pairs_partials() doubles (one record of 1 + M + M (M - 1) / 2
+ * per tile, floor(N / 64) + G tiles at the most); ticket as gine_pool_score.  Validation as
+ * gine_pool_score, and num_segments >= 1, before any HIP call; num_nodes = 0 launches nothing.
+ * ---------------------------------------------------------------------------------- */
+int gine_pool_pairs_partials(int64_t num_nodes, int32_t num_members, int64_t num_segments,
+                             size_t* count);
+int gine_pool_pairs(const float* preds, const float* y, int32_t num_members, int64_t num_nodes,
+                    int32_t kind, double u, double xi, double c, const double* jacobi_nodes,
+                    const double* jacobi_weights, const int64_t* ptr, int64_t num_segments,
+                    double* count, double* member_crps, double* distance, double* partials,
+                    uint32_t* ticket, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The raw ensemble beside that distribution: M <= 64 members per row (one wavefront a row),
  * read in place from a strided fp32 view: member i of row n is
  *   x = shift + scale * (double)members[n * row_stride + i * member_stride]

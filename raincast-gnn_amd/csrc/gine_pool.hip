@@ -7,6 +7,8 @@
 // the members' closed forms minus the pool's diversity V, which has none and is integrated
 // by a fixed rule (16-point Gauss-Legendre between sorted breakpoints, one 32-point
 // Gauss-Jacobi panel for the Pareto tails).  Every result and all arithmetic fp64.
+// For fitting the weights, gine_pool_pairs sums per segment of rows what that
+// CRPS needs as a function of w: the members' CRPS and the pairwise int (F_m - F_l)^2 dx.
 //
 // RowP, load_row, cdf_at, sf_at, quantile_at and crps_row are restated from
 // gine_forecast.hip expression for expression (that file's kernels stay what they are): a
@@ -576,6 +578,246 @@ __global__ __launch_bounds__(kThreads) void k_pool_score(
   if (tid == 0) *ticket = 0u;  // re-armed for the next call (stream order)
 }
 
+// Pair sums for fitting the pool's weights.  Over the rows of a segment that have
+// a target: their number, every member's closed-form CRPS, and for every pair m < l the Cramer
+// distance int (F_m - F_l)^2 dx by the row's own rule above -- the breakpoints of ALL M members,
+// so that V(w) = 1/2 w' D w holds node by node.
+//
+// A workgroup owns one tile: up to 64 consecutive rows of one segment, taken in order.  Tile k
+// of segment g is block ptr[g] / 64 + g + k: that start grows with g, so a block finds its
+// segment by bisection, and floor(N / 64) + G blocks cover every tile (some own none).  Per row
+// the panels that are not empty are listed in order, and their nodes (the tail panel's last) go
+// through LDS in chunks of 128: every lane evaluates members at nodes into s_f[node][member]
+// (odd row stride), then the lane of pair (m, l) and node slice s adds wq (F_m - F_l)^2 for the
+// chunk's nodes s, s + S, ... in order; S = 256 / pairs slices when there are fewer than 256
+// pairs, else one slice and up to two pairs a lane.  At the row's end its slices are added in
+// order: the row's own value, which joins the tile's sum; the tile's record [count, crps_m,
+// pairs] is written after its last row.  The workgroup that draws the last ticket adds the records of each segment: R = 1 + M
+// + pairs entries, the tiles cut into 256 / R contiguous runs (one above 256 entries), each run
+// summed in tile order and the runs in order.  All of it a function of M and the segment's rows.
+constexpr int kPairChunk = 128;
+constexpr int kPairMax = kPoolMaxM * (kPoolMaxM - 1) / 2;  // 496
+constexpr int kPairRec = 1 + kPoolMaxM + kPairMax;          // 529
+
+__device__ __forceinline__ void pair_unpack(int p, int M, int& m, int& l) {
+  m = 0;
+  for (int i = 0; i < kPoolMaxM; ++i) {  // (0,1), (0,2), ..., (M-2, M-1)
+    if (p < M - 1 - m) break;
+    p -= M - 1 - m;
+    ++m;
+  }
+  l = m + 1 + p;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_pool_pairs(
+    const float* __restrict__ preds, const float* __restrict__ y, int M, int64_t n,
+    double u_fixed, double xi, double c, const double* __restrict__ gj_x,
+    const double* __restrict__ gj_w, const int64_t* __restrict__ ptr, int64_t G,
+    double* __restrict__ count, double* __restrict__ cbar, double* __restrict__ dist,
+    double* __restrict__ partials, unsigned int* __restrict__ ticket) {
+  __shared__ RowP s_row[kPoolMaxM];
+  __shared__ double s_raw[kPoolMaxBp];
+  __shared__ double s_bp[kPoolMaxBp];
+  __shared__ int s_pan[kPoolMaxBp];
+  __shared__ double s_f[kPairChunk * (kPoolMaxM + 1)];
+  __shared__ double s_x[kPairChunk];
+  __shared__ double s_wq[kPairChunk];
+  __shared__ double s_acc[kPairRec];
+  __shared__ int s_npan;
+  __shared__ int s_last;
+  constexpr int K = Kind<KIND>::K;
+  constexpr bool atom = Kind<KIND>::atom, tail = Kind<KIND>::tail;
+  const double inf = __builtin_huge_val();
+  const int tid = threadIdx.x;
+  const int P = M * (M - 1) / 2, R = 1 + M + P;
+  const int stride = M | 1;
+  // this block's tile
+  const int64_t blk = blockIdx.x;
+  int64_t g = 0, top = G - 1;
+  for (int it = 0; it < 64; ++it) {  // the last g with ptr[g] / 64 + g <= blk
+    if (g >= top) break;
+    const int64_t mid = g + (top - g + 1) / 2;
+    if (ptr[mid] / kRows + mid <= blk) g = mid;
+    else top = mid - 1;
+  }
+  const int64_t seg_a = min<int64_t>(max<int64_t>(ptr[g], 0), n);
+  const int64_t seg_e = min<int64_t>(max<int64_t>(ptr[g + 1], seg_a), n);
+  const int64_t tile = blk - (ptr[g] / kRows + g);
+  const bool owns = tile >= 0 && tile < ceil_div(seg_e - seg_a, (int64_t)kRows);
+  const int64_t first = seg_a + (owns ? tile : 0) * kRows;
+  const int rows = owns ? (int)min<int64_t>(kRows, seg_e - first) : 0;
+  // this lane's pairs and node slice
+  const int S = P >= kThreads ? 1 : (P > 0 ? kThreads / P : 0);
+  const bool on0 = tid < P * S;
+  const int sl = on0 ? tid / P : 0;
+  const bool on1 = tid + kThreads < P;
+  int m0 = 0, l0 = 0, m1 = 0, l1 = 0;
+  if (on0) pair_unpack(tid - sl * P, M, m0, l0);
+  if (on1) pair_unpack(tid + kThreads, M, m1, l1);
+  double sum0 = 0.0, sum1 = 0.0, cacc = 0.0, cnt = 0.0;
+  for (int rr = 0; rr < rows; ++rr) {
+    double acc0 = 0.0, acc1 = 0.0;
+    const int64_t row = first + rr;
+    const float yf = y[row];
+    if (!(yf == yf)) continue;  // no target: the row adds nothing (the whole workgroup)
+    __syncthreads();            // the row before is done with LDS
+    if (tid < M) s_row[tid] = load_row<KIND>(preds + (int64_t)tid * n * K, row, u_fixed, c);
+    __syncthreads();
+    if (tid < M) cacc += crps_row<KIND>(s_row[tid], (double)yf, c, xi);
+    cnt += 1.0;
+    if (P == 0) continue;
+    // breakpoints, clipped and ranked as k_pool_score builds them
+    double U = -inf, Sg = 0.0, lo = inf, hi = -inf;
+    for (int m = 0; m < M; ++m) {
+      U = fmax(U, s_row[m].u);
+      Sg = fmax(Sg, s_row[m].su);
+      lo = fmin(lo, s_row[m].mu + kBpK[0] * s_row[m].sigma);
+      hi = fmax(hi, s_row[m].mu + kBpK[kPoolK - 1] * s_row[m].sigma);
+    }
+    if constexpr (atom) lo = c;
+    if constexpr (tail) hi = U;
+    else if constexpr (atom) hi = fmax(hi, c);
+    const int nb = kPoolK * M + (tail ? M : 0) + (atom ? 1 : 0);
+    for (int j = tid; j < nb; j += kThreads) {
+      double b;
+      if (j < kPoolK * M) {
+        const int m = j / kPoolK, k = j - m * kPoolK;
+        b = s_row[m].mu + kBpK[k] * s_row[m].sigma;
+      } else if (tail && j < (kPoolK + 1) * M) {
+        b = s_row[j - kPoolK * M].u;
+      } else {
+        b = c;
+      }
+      s_raw[j] = fmin(fmax(b, lo), hi);
+    }
+    __syncthreads();
+    for (int j = tid; j < nb; j += kThreads) {
+      const double b = s_raw[j];
+      int rank = 0;
+      for (int i = 0; i < nb; ++i) {
+        const double o = s_raw[i];
+        rank += (o < b || (o == b && i < j)) ? 1 : 0;
+      }
+      s_bp[rank] = b;
+    }
+    __syncthreads();
+    // the panels that are not empty, in order
+    for (int j = tid; j < nb - 1; j += kThreads) {
+      int before = 0;
+      for (int i = 0; i < j; ++i) before += 0.5 * (s_bp[i + 1] - s_bp[i]) != 0.0 ? 1 : 0;
+      const bool full = 0.5 * (s_bp[j + 1] - s_bp[j]) != 0.0;
+      if (full) s_pan[before] = j;
+      if (j == nb - 2) s_npan = before + (full ? 1 : 0);
+    }
+    __syncthreads();
+    const int body = kGL * s_npan;
+    const int total = body + (tail ? kGJ : 0);
+    for (int cb = 0; cb < total; cb += kPairChunk) {
+      const int cn = min(kPairChunk, total - cb);
+      if (tid < cn) {
+        const int idx = cb + tid;
+        if (idx < body) {
+          const int p = s_pan[idx / kGL], i = idx % kGL;
+          const double a = s_bp[p], b = s_bp[p + 1];
+          const double half = 0.5 * (b - a);
+          const double node = i < 8 ? -kGLx[7 - i] : kGLx[i - 8];
+          s_wq[tid] = half * (i < 8 ? kGLw[7 - i] : kGLw[i - 8]);
+          s_x[tid] = 0.5 * (a + b) + half * node;
+        } else {
+          // x = U + (S / xi) (1 - w) / w; the rule's weight times dx/dw over its own w^(2/xi - 2)
+          const double wn = gj_x[idx - body];
+          s_x[tid] = U + (Sg / xi) * ((1.0 - wn) / wn);
+          s_wq[tid] = gj_w[idx - body] * ((Sg / xi) * pow(wn, -2.0 / xi));
+        }
+      }
+      __syncthreads();
+      for (int idx = tid; idx < cn * M; idx += kThreads) {  // lanes side by side: one member
+        const int m = idx / cn, nd = idx - m * cn;
+        const double xq = s_x[nd];
+        s_f[nd * stride + m] = cb + nd < body ? cdf_at<KIND>(s_row[m], xq, c, xi)
+                                              : sf_at<KIND>(s_row[m], xq, c, xi);
+      }
+      __syncthreads();
+      if (on0) {
+        for (int nd = sl; nd < cn; nd += S) {
+          const double d = s_f[nd * stride + m0] - s_f[nd * stride + l0];
+          acc0 += s_wq[nd] * d * d;
+        }
+      }
+      if (on1) {
+        for (int nd = 0; nd < cn; ++nd) {
+          const double d = s_f[nd * stride + m1] - s_f[nd * stride + l1];
+          acc1 += s_wq[nd] * d * d;
+        }
+      }
+      __syncthreads();
+    }
+    // the row's value of a pair: its node slices in order; then the rows in order
+    if (S > 1) {
+      if (on0) s_f[tid] = acc0;  // [slice][pair]
+      __syncthreads();
+      if (tid < P) {
+        acc0 = s_f[tid];
+        for (int s = 1; s < S; ++s) acc0 += s_f[s * P + tid];
+      }
+    }
+    sum0 += acc0;
+    sum1 += acc1;
+  }
+  if (owns) {
+    double* rec = partials + (size_t)blk * (size_t)R;
+    if (tid == 0) __hip_atomic_exchange(&rec[0], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < M)
+      __hip_atomic_exchange(&rec[1 + tid], cacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < P)
+      __hip_atomic_exchange(&rec[1 + M + tid], sum0, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT);
+    if (on1)
+      __hip_atomic_exchange(&rec[1 + M + kThreads + tid], sum1, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();  // every wave's entries are out
+  if (tid == 0) {
+    const unsigned int prev =
+        __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = prev == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  const int runs = R >= kThreads ? 1 : kThreads / R;
+  for (int64_t sg = 0; sg < G; ++sg) {
+    const int64_t a = min<int64_t>(max<int64_t>(ptr[sg], 0), n);
+    const int64_t e = min<int64_t>(max<int64_t>(ptr[sg + 1], a), n);
+    const int64_t t0 = ptr[sg] / kRows + sg;
+    const int64_t tiles = ceil_div(e - a, (int64_t)kRows);
+    const int64_t per = ceil_div(tiles, (int64_t)runs);
+    for (int it = tid; it < R * runs; it += kThreads) {
+      const int run = it / R, ent = it - run * R;
+      const int64_t kend = min<int64_t>(tiles, (run + 1) * per);
+      double v = 0.0;
+      for (int64_t k = run * per; k < kend; ++k) {
+        const int64_t rec = t0 + k;
+        if (rec >= 0 && rec < (int64_t)gridDim.x)
+          v += __hip_atomic_load(&partials[(size_t)rec * (size_t)R + ent], __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+      }
+      s_acc[it] = v;
+    }
+    __syncthreads();
+    for (int ent = tid; ent < R; ent += kThreads) {
+      double v = s_acc[ent];
+      for (int run = 1; run < runs; ++run) v += s_acc[run * R + ent];
+      if (ent == 0) count[sg] = v;
+      else if (ent <= M) cbar[sg * M + (ent - 1)] = v;
+      else dist[sg * P + (ent - 1 - M)] = v;
+    }
+    __syncthreads();  // s_acc has been read
+  }
+  if (tid == 0) *ticket = 0u;  // re-armed for the next call (stream order)
+}
+
 // members, kind, sizes and the distribution's domain, before any HIP call
 int check_pool(int32_t num_members, int64_t num_nodes, int32_t kind, double u, double xi,
                double c, int64_t points) {
@@ -680,6 +922,59 @@ extern "C" int gine_pool_score(const float* preds, const float* y, int32_t num_m
     default: LAUNCH_POOL_SCORE(GINE_LOSS_MIXED_U); break;
   }
 #undef LAUNCH_POOL_SCORE
+  GINE_LAUNCH_STATUS();
+  return GINE_OK;
+}
+
+// one record per tile: floor(N / 64) + G tiles at the most
+static int pool_pairs_tiles(int64_t num_nodes, int64_t num_segments, int64_t* tiles) {
+  if (num_segments < 1) return GINE_ERR_INVALID;
+  if (num_segments > 0x7fffffff - num_nodes / kRows) return GINE_ERR_TOO_LARGE;
+  *tiles = num_nodes / kRows + num_segments;
+  return GINE_OK;
+}
+
+extern "C" int gine_pool_pairs_partials(int64_t num_nodes, int32_t num_members,
+                                        int64_t num_segments, size_t* count) {
+  if (!count || num_nodes < 0 || num_members < 1 || num_members > kPoolMaxM)
+    return GINE_ERR_INVALID;
+  if (num_nodes > 0x7fffffff) return GINE_ERR_TOO_LARGE;
+  int64_t tiles = 0;
+  const int rc = pool_pairs_tiles(num_nodes, num_segments, &tiles);
+  if (rc != GINE_OK) return rc;
+  *count = (size_t)tiles * (size_t)(1 + num_members + num_members * (num_members - 1) / 2);
+  return GINE_OK;
+}
+
+extern "C" int gine_pool_pairs(const float* preds, const float* y, int32_t num_members,
+                               int64_t num_nodes, int32_t kind, double u, double xi, double c,
+                               const double* jacobi_nodes, const double* jacobi_weights,
+                               const int64_t* ptr, int64_t num_segments, double* count,
+                               double* member_crps, double* distance, double* partials,
+                               uint32_t* ticket, void* stream) {
+  int rc = check_pool(num_members, num_nodes, kind, u, xi, c, 0);
+  if (rc != GINE_OK) return rc;
+  int64_t tiles = 0;
+  rc = pool_pairs_tiles(num_nodes, num_segments, &tiles);
+  if (rc != GINE_OK) return rc;
+  if (num_nodes == 0) return GINE_OK;
+  if (!preds || !y || !ptr || !count || !member_crps || !partials || !ticket)
+    return GINE_ERR_INVALID;
+  if (num_members > 1 && !distance) return GINE_ERR_INVALID;
+  const bool tail = kind == GINE_LOSS_MIXED || kind == GINE_LOSS_MIXED_U;
+  if (tail && (!jacobi_nodes || !jacobi_weights)) return GINE_ERR_INVALID;
+  const dim3 grid((unsigned)tiles);
+#define LAUNCH_POOL_PAIRS(KIND_)                                                               \
+  hipLaunchKernelGGL((k_pool_pairs<KIND_>), grid, dim3(kThreads), 0, as_stream(stream), preds, \
+                     y, (int)num_members, num_nodes, u, xi, c, jacobi_nodes, jacobi_weights,   \
+                     ptr, num_segments, count, member_crps, distance, partials, ticket)
+  switch (kind) {
+    case GINE_LOSS_NORMAL: LAUNCH_POOL_PAIRS(GINE_LOSS_NORMAL); break;
+    case GINE_LOSS_MIXED_NORMAL: LAUNCH_POOL_PAIRS(GINE_LOSS_MIXED_NORMAL); break;
+    case GINE_LOSS_MIXED: LAUNCH_POOL_PAIRS(GINE_LOSS_MIXED); break;
+    default: LAUNCH_POOL_PAIRS(GINE_LOSS_MIXED_U); break;
+  }
+#undef LAUNCH_POOL_PAIRS
   GINE_LAUNCH_STATUS();
   return GINE_OK;
 }

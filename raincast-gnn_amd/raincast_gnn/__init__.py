@@ -19,13 +19,13 @@ from .compare import BootstrapResult, DMResult, PairedScores
 from . import reliability
 from .reliability import Reliability, ReliabilityBands, ReliabilityFit
 from . import pool
-from .pool import ForecastPool, PoolScore
+from .pool import ForecastPool, PairSums, PoolFit, PoolScore
 
 __all__ = ["AreaScore", "BootstrapResult", "DMResult", "EnsembleScore", "EnsembleTwScore",
            "FEATURE_NAMES", "FeatureImportance", "FieldScore", "Forecast", "ForecastPool",
            "ForecastScore",
-           "GINEConv", "GineGraph", "MemberFields", "PairedScores", "PermutationPlan",
-           "PoolScore", "Predictor", "RawEnsemble", "Reliability", "ReliabilityBands", "ReliabilityFit",
+           "GINEConv", "GineGraph", "MemberFields", "PairSums", "PairedScores", "PermutationPlan",
+           "PoolFit", "PoolScore", "Predictor", "RawEnsemble", "Reliability", "ReliabilityBands", "ReliabilityFit",
            "TwScore", "compare", "fill_batch", "get_graph", "graph_cache", "native_library",
            "permutation_importance", "pit_sample", "pool", "reliability", "skill"]
 

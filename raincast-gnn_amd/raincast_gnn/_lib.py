@@ -200,6 +200,9 @@ _SIGNATURES = {
     "gine_pool_score_partials": [_i64, _i32, ctypes.POINTER(_size)],
     "gine_pool_score": [_c_void_p, _c_void_p, _i32, _i64, _i32, _f64, _f64, _f64, _c_void_p,
                         _c_void_p, _i32] + [_c_void_p] * 12,
+    "gine_pool_pairs_partials": [_i64, _i32, _i64, ctypes.POINTER(_size)],
+    "gine_pool_pairs": [_c_void_p, _c_void_p, _i32, _i64, _i32, _f64, _f64, _f64, _c_void_p,
+                        _c_void_p, _c_void_p, _i64] + [_c_void_p] * 6,
     "gine_ensemble_score": [_c_void_p, _i64, _i64, _i32, _f64, _f64, _c_void_p, _i64, _c_void_p,
                             _i32] + [_c_void_p] * 7,
     "gine_ensemble_ecc": [_c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i64, _i64, _i32,

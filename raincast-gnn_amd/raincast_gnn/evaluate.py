@@ -115,6 +115,18 @@ def verify_pool(model: torch.nn.Module, stacked: torch.Tensor, targets: torch.Te
     return PoolVerification(pool, average, pool.crps, average.crps, member, diversity)
 
 
+def fit_pool(model: torch.nn.Module, stacked: torch.Tensor, targets: torch.Tensor, folds=5):
+    """The weights of minimum mean CRPS for the linear pool of ``stacked [M, N, K]`` on the rows
+    with a target, cross-validated over ``folds`` contiguous blocks of rows
+    (:meth:`raincast_gnn.pool.ForecastPool.fit_weights`).  Returns the
+    :class:`raincast_gnn.pool.PoolFit` and the pool under the fitted weights (the members of
+    weight 0 dropped)."""
+    from .pool import ForecastPool
+    pool = ForecastPool.from_model(model, stacked)
+    fit = pool.fit_weights(targets, folds=folds)
+    return fit, pool.reweighted(fit.weights)
+
+
 @dataclass
 class EnsembleVerification:
     """What :func:`verify_against_ensemble` returns; unpacks as ``(forecast, ensemble,
