@@ -63,7 +63,9 @@ extern "C" {
                                   gine_compare_reduce / _bootstrap / _dm: paired score
                                   comparison (block bootstrap, Diebold-Mariano),
                                   gine_reliability_counts / _fit / _resample: reliability
-                                  diagrams (CORP curves, consistency bands, MCB / DSC / UNC) */
+                                  diagrams (CORP curves, consistency bands, MCB / DSC / UNC),
+                                  gine_emos_predictors / _fit / _predict: the per-station EMOS
+                                  baseline fitted by minimum CRPS */
 
 #define GINE_OK 0
 #define GINE_ERR_INVALID 1    /* null pointer, negative size, bad flag */
@@ -903,6 +905,55 @@ int gine_ensemble_ecc(const float* pred, int64_t num_nodes, int32_t kind, double
                       double c, const float* members, int64_t row_stride, int64_t member_stride,
                       int32_t num_members, double scale, double shift, int32_t flags,
                       double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * EMOS: the ensemble's summary statistics mapped affinely to the parameters of the loss's
+ * distribution, the coefficients fitted per group of rows by minimum CRPS (additive in ABI
+ * 10).  kind: GINE_LOSS_NORMAL / MIXED_NORMAL / MIXED (K = 2, 3, 4 columns,
+ * P = 2 K coefficients); GINE_LOSS_MIXED_U is GINE_ERR_INVALID (its u is a per-row network
+ * output).  Per row, with x_i as gine_ensemble_score (NaN = missing, m valid members):
+ *   mean = (1/m) sum x_i, sd = sqrt((1/m) sum (x_i - mean)^2), dry = #{x_i <= c} / m,
+ * fp64, summed in member order; z = (mean, sd, dry, sd), raw_k = theta[2k] + theta[2k+1] z_k,
+ *   mu = raw_0, sigma = softplus(raw_1) + 1e-6, p = sigmoid(raw_2),
+ *   sigma_u = softplus(raw_3) + 1e-6, softplus(x) = max(x, 0) + log1p(exp(-|x|)).
+ * Rows are in collated order (row = day * num_stations + station); num_stations = 0 is one
+ * global group.  The pack [R, 4] fp64 = (mean, sd, dry, y) is group-major: row n lies at
+ * (n % S) * (N / S) + n / S (at n for S = 0).
+ * gine_emos_predictors: members / strides / scale / shift as gine_ensemble_score, y [N] fp32
+ *   or NULL (then NaN); writes the pack; rows without a valid member get NaN predictors.
+ * gine_emos_fit: ptr [num_groups + 1] int64 on the device (contiguous segments of pack rows as
+ *   gine_pool_pairs; the caller validates it, the kernel clamps it into 0..num_rows).  Per
+ *   group over its valid rows (a target and m >= 1), from theta0 = (0, 1, b, 0, 0, 0, b, 0)
+ *   truncated to P, b = log(e - 1):
+ *     J(theta) = (1/n) sum crps(pred(theta; row), y) + ridge |theta - theta0|^2,
+ *   crps the closed form of gine_crps_fwd for the kind (fixed u), minimised by BFGS on the
+ *   inverse Hessian: H = I; stop with status 0 when max|g| <= gtol max(1, |J|); d = -H g, and
+ *   H = I, d = -g unless g.d < 0; Armijo backtracking with c1 = 1e-4 over the steps 1, 1/2,
+ *   ..., 2^-40 (a non-finite J fails); H updated when s.y > 1e-10 |s| |y|; at most max_iter
+ *   iterations.  theta [G, P]; report [G, 8] fp64 = J, mean CRPS without the ridge term,
+ *   max|g|, iterations, evaluations, valid rows, status, 0.  status: 0 converged, 1 iteration
+ *   limit, 2 no decrease along d (theta: the last accepted point), 3 fewer than min_rows
+ *   valid rows (theta = theta0; J, CRPS and max|g| NaN).  One 256-thread workgroup per group,
+ *   sums in a fixed order, no atomics: a group's bits depend on its rows alone.
+ * gine_emos_predict: pred [N, K] fp32 in collated order from the pack of the same rows and
+ *   num_stations and theta [G, P] (G = num_stations, or 1 for 0); NaN rows where mean is NaN.
+ * Before any HIP call: GINE_ERR_INVALID for a bad kind, num_members outside 1..64, a negative
+ * size or stride, num_rows not a multiple of num_stations, xi outside (0, 1) or u <= c for
+ * MIXED, a negative or non-finite ridge or gtol, max_iter outside 0..GINE_EMOS_MAX_ITER,
+ * min_rows < 1 or a NULL operand.  Zero rows or groups: GINE_OK, nothing launched.  One launch
+ * each, no workspace, no host synchronisation (capturable).
+ * ---------------------------------------------------------------------------------- */
+#define GINE_EMOS_MAX_ITER 10000
+int gine_emos_predictors(const float* members, int64_t row_stride, int64_t member_stride,
+                         int32_t num_members, double scale, double shift, double c,
+                         const float* y, int64_t num_rows, int64_t num_stations, double* pack,
+                         void* stream);
+int gine_emos_fit(const double* pack, const int64_t* ptr, int64_t num_groups, int64_t num_rows,
+                  int32_t kind, double u, double xi, double c, double ridge, double gtol,
+                  int32_t max_iter, int32_t min_rows, double* theta, double* report,
+                  void* stream);
+int gine_emos_predict(const double* pack, const double* theta, int64_t num_rows,
+                      int64_t num_stations, int32_t kind, float* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Threshold-weighted CRPS, weight 1{x >= t}, in model space, fp64 per row:

@@ -20,13 +20,16 @@ from . import reliability
 from .reliability import Reliability, ReliabilityBands, ReliabilityFit
 from . import pool
 from .pool import ForecastPool, PairSums, PoolFit, PoolScore
+from . import emos
+from .emos import Emos, EmosFit
 
-__all__ = ["AreaScore", "BootstrapResult", "DMResult", "EnsembleScore", "EnsembleTwScore",
+__all__ = ["AreaScore", "BootstrapResult", "DMResult", "Emos", "EmosFit", "EnsembleScore",
+           "EnsembleTwScore",
            "FEATURE_NAMES", "FeatureImportance", "FieldScore", "Forecast", "ForecastPool",
            "ForecastScore",
            "GINEConv", "GineGraph", "MemberFields", "PairSums", "PairedScores", "PermutationPlan",
            "PoolFit", "PoolScore", "Predictor", "RawEnsemble", "Reliability", "ReliabilityBands", "ReliabilityFit",
-           "TwScore", "compare", "fill_batch", "get_graph", "graph_cache", "native_library",
+           "TwScore", "compare", "emos", "fill_batch", "get_graph", "graph_cache", "native_library",
            "permutation_importance", "pit_sample", "pool", "reliability", "skill"]
 
 

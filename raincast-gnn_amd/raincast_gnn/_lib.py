@@ -39,6 +39,7 @@ RELIABILITY_REPS_PER_BLOCK = 1  # GINE_RELIABILITY_REPS_PER_BLOCK
 RELIABILITY_AUTO, RELIABILITY_ATOMIC, RELIABILITY_BALLOT = 0, 1, 2  # GINE_RELIABILITY_*
 RELIABILITY_BALLOT_MAX_LEVELS = 64  # the ballot traversal: one lane per level
 BATCH_MAX_FEATURES = 64  # gine_batch_fill_permuted: the bits of col_mask
+EMOS_MAX_ITER = 10000  # GINE_EMOS_MAX_ITER
 
 _c_void_p = ctypes.c_void_p
 _i32, _i64, _f32, _size = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
@@ -207,6 +208,11 @@ _SIGNATURES = {
                             _i32] + [_c_void_p] * 7,
     "gine_ensemble_ecc": [_c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i64, _i64, _i32,
                           _f64, _f64, _i32, _c_void_p, _c_void_p],
+    "gine_emos_predictors": [_c_void_p, _i64, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i64, _i64,
+                             _c_void_p, _c_void_p],
+    "gine_emos_fit": [_c_void_p, _c_void_p, _i64, _i64, _i32, _f64, _f64, _f64, _f64, _f64, _i32,
+                      _i32, _c_void_p, _c_void_p, _c_void_p],
+    "gine_emos_predict": [_c_void_p, _c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p],
     "gine_forecast_twcrps_partials": [_i64, _i32, ctypes.POINTER(_size)],
     "gine_forecast_twcrps": [_c_void_p, _c_void_p, _i64, _i32, _f64, _f64, _f64, _c_void_p, _i32]
                             + [_c_void_p] * 6,

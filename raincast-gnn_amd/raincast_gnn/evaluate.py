@@ -159,6 +159,57 @@ def verify_against_ensemble(model: torch.nn.Module, preds: torch.Tensor, targets
     return EnsembleVerification(fs, es, skill(model_crps, ens_crps), model_crps, ens_crps, count)
 
 
+def fit_emos(model: torch.nn.Module, raw_train, y_train: torch.Tensor, num_stations=None, **kw):
+    """The EMOS baseline of the model's own distribution, fitted per station by minimum CRPS on
+    the training rows (``raw_train``: a :class:`raincast_gnn.ensemble.RawEnsemble`, rows in
+    collated order; ``num_stations=None``: one global parameter set).  Keywords go to
+    :class:`raincast_gnn.emos.Emos` (``ridge``, ``gtol``, ``max_iter``, ``min_rows``).  Returns
+    the :class:`raincast_gnn.emos.EmosFit`."""
+    from .emos import Emos
+    return Emos.from_model(model, **kw).fit(raw_train, y_train, num_stations)
+
+
+@dataclass
+class EmosVerification:
+    """What :func:`verify_against_emos` returns; unpacks as ``(forecast, emos, crpss)``.
+    ``forecast`` / ``emos``: the :class:`raincast_gnn.forecast.ForecastScore` of the model and
+    of EMOS on the same rows; the two mean CRPS values and ``crpss = 1 - model / emos`` are
+    over the ``valid`` rows (a value in both); ``model_rows`` / ``emos_rows`` are the two
+    ``crps_rows`` on one device, as :func:`compare` takes them."""
+    forecast: object
+    emos: object
+    crpss: torch.Tensor
+    model_crps: torch.Tensor
+    emos_crps: torch.Tensor
+    valid: torch.Tensor
+    model_rows: torch.Tensor
+    emos_rows: torch.Tensor
+
+    def __iter__(self):
+        return iter((self.forecast, self.emos, self.crpss))
+
+
+def verify_against_emos(model: torch.nn.Module, preds: torch.Tensor, targets: torch.Tensor, raw,
+                        fit, num_stations, thresholds, unit: str = "mm") -> EmosVerification:
+    """:func:`verify` beside the same scores of the EMOS baseline ``fit`` (:func:`fit_emos`, on
+    training rows) applied to ``raw``, the raw ensemble of the rows of ``preds``, and the skill
+    ``CRPSS = 1 - CRPS_model / CRPS_emos`` over the rows valid in both: the skill that says
+    something, the raw ensemble being uncalibrated."""
+    from .emos import Emos
+    from .ensemble import skill
+    fs = verify(model, preds, targets, thresholds, unit=unit)
+    es = Emos.from_model(model).forecast(raw, fit, num_stations).score(targets, thresholds,
+                                                                       unit=unit)
+    er = es.crps_rows.to(fs.crps_rows.device)
+    both = ~torch.isnan(fs.crps_rows) & ~torch.isnan(er)
+    count = both.sum().double()
+    zero = torch.zeros_like(fs.crps_rows)
+    model_crps = torch.where(both, fs.crps_rows, zero).sum() / count
+    emos_crps = torch.where(both, er, zero).sum() / count
+    return EmosVerification(fs, es, skill(model_crps, emos_crps), model_crps, emos_crps, count,
+                            fs.crps_rows, er)
+
+
 @dataclass
 class FieldVerification:
     """What :func:`verify_fields` returns: the :class:`raincast_gnn.fields.FieldScore` of the
