@@ -1291,6 +1291,16 @@ int gine_deepset_fwd_fold2(const float* ens, const float* w1, const float* b1, f
                            const float* br1, const float* wdr, const float* bdr, float* wfold,
                            int32_t x_features, const float* wr0, const float* br0,
                            const float* wp2, const float* bp2, float* wfold2, void* stream);
+/* Testing only: on != 0 keeps every DeepSet launch (gine_deepset_fwd, _fwd_fold2, _bwd,
+ * _bwd_chain) on the generic tile stager; 0 (the default) lets a launch whose walks hold only
+ * full tiles -- 16-node halves, num_nodes % 32 == 0, hidden in {64, 128}, ens on a 16-byte
+ * boundary -- stage them with 16-byte loads and no per-element range tests.  Both stagers
+ * give the same bits everywhere; the generic one is the tests' reference for the fast one. */
+int gine_testing_deepset_generic_stager(int32_t on);
+/* Testing only: *full_tiles = 1 when a DeepSet launch on this ens pointer, node count and hidden
+ * width would take the full-tile stager (under the switch above as it stands), else 0. */
+int gine_testing_deepset_stager(const float* ens, int64_t num_nodes, int32_t hidden,
+                                int32_t* full_tiles);
 int gine_deepset_bwd_num_partials(int64_t num_nodes, int32_t hidden, int32_t* num_partials);
 int gine_deepset_bwd(const float* ens, const uint16_t* mask, const float* dr, float* slab,
                      float* dw1, float* db1, int64_t num_nodes, int32_t members,

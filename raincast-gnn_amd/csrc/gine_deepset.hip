@@ -24,6 +24,8 @@
 #include "gine_chainrow.hpp"
 
 #include <algorithm>
+#include <atomic>
+#include <cstdint>
 #include <type_traits>
 
 namespace gine {
@@ -225,6 +227,116 @@ struct Stager {
   }
 };
 
+// The stager of a walk that holds only full tiles of an aligned ens (G = 16, N % 32 == 0, ens
+// on a 16-byte boundary: the host knows, ds_fast_ok below): no row of such a tile is padding
+// or past the last row, so nothing is range-tested, no `ok` bit is formed and no zero is
+// selected -- per tile a thread issues its loads and its stores and nothing else.  A tile's
+// two runs are 16*F contiguous floats that start at multiples of 16*F floats, so a run is
+// 4*F whole float4s on 16-byte boundaries and a float4 never crosses a run's end: the first
+// NV float4s per thread (NV = the rounds every thread takes at the smallest F that pads to
+// KP) are 16-byte loads, the rest of the tile goes as dwords (PS rounds, as the generic
+// stager's; a thread without an element loads the tile's first float and stores it to its
+// dummy slot).  A loaded vector's four elements go to their own rows and columns (F need not
+// be a multiple of 4), so every cell a chain reads holds the generic stager's bits.  (Only
+// the dummy slots differ -- columns KP.. / KX.. and rows 32.., which no chain reads: the
+// generic stager stores its zero there, this one whatever value it loaded.)
+// Smallest F that pads to KP (pad_fwd / pad_bwd below)
+constexpr int ds_fmin(int KP, bool bwd) {
+  return KP == 16 ? 1 : KP == 32 ? 17 : KP == 36 ? 33 : KP == 40 ? (bwd ? 37 : 33)
+                                                              : KP == 48 ? 41 : 49;
+}
+template <int NT, int KP, bool X3 = false, int KI = 0, bool BWD = false>
+struct FastStager {
+  using Gen = Stager<NT, KP, false, X3, KI, BWD>;
+  static constexpr int NV = 8 * ds_fmin(KP, BWD) / NT;
+  static constexpr int PS = (32 * KP - 4 * NT * NV + NT - 1) / NT;
+  static constexpr int PER = 4 * NV + PS;
+  static constexpr int LD = Gen::LD;
+  static_assert(PS >= 0 && PER > 0, "rounds");
+  int src[NV + PS];  // float offset from the tile's first row (vectors: of element 0)
+  int dst[PER];      // LDS offset of every element
+  __device__ static int place(int c, int j, int f) {
+    if constexpr (X3 && KI != 0) return f * LD + (16 * c + j);  // col-major
+    else return (16 * c + j) * LD + f;
+  }
+  __device__ __forceinline__ void init(int F, int M, int G) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int e = 4 * (threadIdx.x + i * NT);  // < 32*F: NV <= 8*F / NT
+      const int c = e >= 16 * F ? 1 : 0;
+      const int off = e - c * 16 * F;
+      src[i] = c * G * M * F + off;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int j = (off + k) / F, f = (off + k) - j * F;
+        dst[4 * i + k] = place(c, j, f);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < PS; ++i) {
+      const int e = 4 * NT * NV + threadIdx.x + i * NT;
+      const int c = e >= 16 * F ? 1 : 0;
+      const int off = e - c * 16 * F;
+      const int j = off / F, f = off - j * F;
+      const bool has = e < 32 * F;
+      src[NV + i] = has ? c * G * M * F + off : 0;
+      dst[4 * NV + i] = has ? place(c, j, f) : Gen::dummy_slot();
+    }
+  }
+  // Same signature as Stager::load; the tile is full and in range, so the limits go unused.
+  __device__ __forceinline__ uint32_t load(float (&v)[PER], const float* __restrict__ ens,
+                                           int64_t row0, int64_t rows_total, int F,
+                                           int /*half_lim*/) const {
+    const float* __restrict__ base = ens + row0 * F;
+#ifdef GINE_BOUNDS_CHECK
+#pragma unroll
+    for (int i = 0; i < NV + PS; ++i) {
+      const int64_t a = (base - ens) + src[i], w = i < NV ? 4 : 1;
+      if (a < 0 || a + w > rows_total * F || (i < NV && ((uintptr_t)(base + src[i]) & 15))) {
+        printf("GINE_BOUNDS_CHECK deepset FastStager::load: block %d thread %d reads "
+               "ens[%lld..+%d] outside [0, %lld) or unaligned\n", (int)blockIdx.x,
+               (int)threadIdx.x, (long long)a, (int)w, (long long)(rows_total * F));
+        __builtin_trap();
+      }
+    }
+#endif
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const float4 t = *reinterpret_cast<const float4*>(base + src[i]);
+      v[4 * i] = t.x;
+      v[4 * i + 1] = t.y;
+      v[4 * i + 2] = t.z;
+      v[4 * i + 3] = t.w;
+    }
+#pragma unroll
+    for (int i = 0; i < PS; ++i) v[4 * NV + i] = base[src[NV + i]];
+    return 0u;
+  }
+  __device__ __forceinline__ void store(float* s_e, const float (&v)[PER], uint32_t) const {
+    if constexpr (X3) {
+      constexpr int PL = Gen::kPlane;
+      uint16_t* img = reinterpret_cast<uint16_t*>(s_e);
+#pragma unroll
+      for (int i = 0; i < PER; i += 2) {  // values split in pairs (v_cvt_pk_bf16_f32)
+        const int i1 = i + 1 < PER ? i + 1 : i;
+        uint32_t ph, pm, pl;
+        split2(v[i], v[i1], ph, pm, pl);
+        img[dst[i]] = (uint16_t)ph;
+        img[PL + dst[i]] = (uint16_t)pm;
+        img[2 * PL + dst[i]] = (uint16_t)pl;
+        if (i + 1 < PER) {
+          img[dst[i1]] = (uint16_t)(ph >> 16);
+          img[PL + dst[i1]] = (uint16_t)(pm >> 16);
+          img[2 * PL + dst[i1]] = (uint16_t)(pl >> 16);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < PER; ++i) s_e[dst[i]] = v[i];
+    }
+  }
+};
+
 template <int KP>
 __device__ __forceinline__ void zero_pad(float* s_e, int F) {
   constexpr int LD = KP + 4;
@@ -383,16 +495,15 @@ struct Cursor {
 struct NoPrologue {
   __device__ __forceinline__ void operator()() const {}
 };
-template <bool UNCOND, bool MASKIN, int NT, int KP, bool PAD, bool X3, int KI, bool BWD,
-          class Body, class Pro = NoPrologue>
-__device__ __forceinline__ void walk_tiles(const Groups& gr, int GM, int tpg,
-                                           const Stager<NT, KP, PAD, X3, KI, BWD>& st,
+// St: Stager or FastStager; NT: the workgroup's threads
+template <bool UNCOND, bool MASKIN, int NT, class St, class Body, class Pro = NoPrologue>
+__device__ __forceinline__ void walk_tiles(const Groups& gr, int GM, int tpg, const St& st,
                                            const float* __restrict__ ens, int64_t rows_total,
                                            int F, float* buf0, float* buf1,
                                            const uint16_t* __restrict__ mask_in, Body&& tile,
                                            Pro pro = Pro()) {
   constexpr bool kPro = !std::is_same<Pro, NoPrologue>::value;
-  constexpr int PER = Stager<NT, KP, PAD, X3, KI, BWD>::PER;
+  constexpr int PER = St::PER;
   if (gr.first >= gr.end) return;
   const int count = ((gr.end - gr.first + gr.step - 1) / gr.step) * tpg;
   Cursor cur, pf;  // tile being computed, tile being loaded
@@ -472,7 +583,12 @@ __device__ __forceinline__ void walk_tiles(const Groups& gr, int GM, int tpg,
 #ifndef GINE_DS_FWD_UNCOND
 #define GINE_DS_FWD_UNCOND 0
 #endif
-template <int H, int KP, int G, bool MASK, bool FOLD = false>
+// GT: G, or kFullTiles: 16-node halves and a walk that holds only full tiles of an aligned
+// ens (FastStager).  (The kernel itself and not a wrapper around a shared body, and no further
+// template parameter: either changed the code or the names of the generic instantiations,
+// whose scratch use tests/test_isa.py holds to a committed ceiling per kernel name.)
+constexpr int kFullTiles = -16;
+template <int H, int KP, int GT, bool MASK, bool FOLD = false>
 __global__ __launch_bounds__(2 * H, 4) void k_deepset_fwd(const float* __restrict__ ens,
                                                        const float* __restrict__ w1,
                                                        const float* __restrict__ b1,
@@ -481,6 +597,8 @@ __global__ __launch_bounds__(2 * H, 4) void k_deepset_fwd(const float* __restric
                                                        int64_t N, int M, int F,
                                                        int num_groups, FoldArgs fold,
                                                        Fold2Args fold2) {
+  constexpr bool FAST = GT == kFullTiles;
+  constexpr int G = FAST ? 16 : GT;
   constexpr int NT = 2 * H;
   // the split chain for the large-batch group size only: at 4,000 nodes (8-node groups) it
   // measured 16.2 against 14.1 us, at 16,000 27.7 against 31.3 (profiles/r04_s15_ds_*.txt)
@@ -522,7 +640,7 @@ __global__ __launch_bounds__(2 * H, 4) void k_deepset_fwd(const float* __restric
   }
   const float bias = b1[col];
 
-  Stager<NT, KP, G != 16, X3> st;
+  std::conditional_t<FAST, FastStager<NT, KP, X3>, Stager<NT, KP, G != 16, X3>> st;
   st.init(F, M, G);
   const Groups gr(num_groups, nbw, bw);
   const int GM = G * M, tpg = tiles_per_group(G, M);
@@ -530,8 +648,8 @@ __global__ __launch_bounds__(2 * H, 4) void k_deepset_fwd(const float* __restric
   float* s_mine = s_r + (G * h) * H + col;  // this lane's column of its half's G nodes
   // uniform walk state: node (0..G-1 within each half's G; G: padding) and rows left in it
   int node = 0, rem = M;
-  walk_tiles<GINE_DS_FWD_UNCOND != 0, false>(gr, GM, tpg, st, ens, N * M, F, s_e[0], s_e[1],
-                                             nullptr,
+  walk_tiles<GINE_DS_FWD_UNCOND != 0, false, NT>(gr, GM, tpg, st, ens, N * M, F, s_e[0],
+                                                 s_e[1], nullptr,
              [&](const Cursor& c, const float* buf, uint32_t) {
     if (c.t == 0) {
       node = 0;
@@ -662,7 +780,8 @@ __device__ __forceinline__ void ds_chain_tile(const DsChainArgs& a, int64_t N, i
 
 // CHAIN (k_deepset_bwd_chain, one group per workgroup): dr is not read but made, by
 // ds_chain_tile in the walk's prologue, from `ch`
-template <int H, int KP, int G, bool X3, bool CHAIN = false>
+// FAST: the walk holds only full tiles of an aligned ens (FastStager)
+template <int H, int KP, int G, bool X3, bool CHAIN = false, bool FAST = false>
 __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
                                             const uint16_t* __restrict__ mask,
                                             const float* __restrict__ dr,
@@ -705,7 +824,9 @@ __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
   for (int j = 0; j < TAIL; ++j) tw[j] = 0.f;
   double gb = 0.0;
 
-  Stager<NT, KP, G != 16, X3, KI, true> st;
+  static_assert(!FAST || G == 16, "full tiles: 16-node halves only");
+  std::conditional_t<FAST, FastStager<NT, KP, X3, KI, true>,
+                     Stager<NT, KP, G != 16, X3, KI, true>> st;
   st.init(F, M, G);
   const Groups gr(num_groups, gridDim.x);
   const int GM = G * M, tpg = tiles_per_group(G, M);
@@ -738,15 +859,38 @@ __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
     }
     float dh[16];
     float gsum = 0.f;
+    // dr of the row's node (0 for nodes >= N; padding rows, whose bits are 0, read node
+    // G - 1's): read when the node changes (uniform), not per row.  (Reading one node ahead,
+    // so that the read is in flight under the rows before it, measured 0.6 us slower at
+    // 16,000 nodes: profiles/ds_issue_diet_ab.txt.)
+    // (H = 32 and 256, and H = 64 with 41 to 48 features, keep a read per row: their kernels
+    // sit at the 256-register limit, and seven of them spilled more with the value kept live
+    // across rows)
+    auto dr_of = [&](int n) { return my_dr[(n < G ? n : G - 1) * H]; };
+    if constexpr ((H == 64 && KP != 48) || H == 128) {
+      float d = dr_of(node);
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {  // independent LDS reads, uniform node walk
-      const float d = my_dr[(node < G ? node : G - 1) * H];  // 0 for nodes >= N
-      const float v = ((bits >> q) & 1u) ? d : 0.f;
-      dh[q] = v;
-      gsum += v;
-      if (--rem == 0) {
-        ++node;
-        rem = M;
+      for (int q = 0; q < 16; ++q) {  // uniform node walk
+        const float v = ((bits >> q) & 1u) ? d : 0.f;
+        dh[q] = v;
+        gsum += v;
+        if (--rem == 0) {
+          ++node;
+          rem = M;
+          d = dr_of(node);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {  // independent LDS reads, uniform node walk
+        const float d = dr_of(node);
+        const float v = ((bits >> q) & 1u) ? d : 0.f;
+        dh[q] = v;
+        gsum += v;
+        if (--rem == 0) {
+          ++node;
+          rem = M;
+        }
       }
     }
     gb += (double)gsum;
@@ -791,13 +935,13 @@ __device__ __forceinline__ bool ds_bwd_body(const float* __restrict__ ens,
   };
   if constexpr (CHAIN) {
     float* sA = s_dr + 2 * G * H;
-    walk_tiles<true, true>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask, tile, [&]() {
+    walk_tiles<true, true, NT>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask, tile, [&]() {
       // one group per workgroup: blockIdx.x's (the launch has num_groups workgroups)
       ds_chain_tile<H>(ch, N, (int64_t)gr.first * 2 * G, sA, sA + 32 * (H + 4), s_dr, wave,
                        c32, h);
     });
   } else {
-    walk_tiles<true, true>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask, tile);
+    walk_tiles<true, true, NT>(gr, GM, tpg, st, ens, N * M, F, s_e0, s_e1, mask, tile);
   }
   if constexpr (X3) {
     bool bad = false;
@@ -837,6 +981,20 @@ constexpr int ds_bwd_lds_floats() {
   return (f32 > x3 ? f32 : x3) + 2 * G * H;
 }
 
+template <int H, int KP, int G, bool FAST>
+__device__ __forceinline__ void ds_bwd_kernel(const float* __restrict__ ens,
+                                                       const uint16_t* __restrict__ mask,
+                                                       const float* __restrict__ dr,
+                                                       float* __restrict__ slab, int64_t N,
+                                                       int M, int F, int num_groups,
+                                                       float* s_lds) {
+#if GINE_DS_BWD_BF16X3
+  if (ds_bwd_body<H, KP, G, true, false, FAST>(ens, mask, dr, slab, N, M, F, num_groups, s_lds)) return;
+  __syncthreads();  // a non-finite operand: the fp32 form
+#endif
+  ds_bwd_body<H, KP, G, false, false, FAST>(ens, mask, dr, slab, N, M, F, num_groups, s_lds);
+}
+
 template <int H, int KP, int G>
 __global__ __launch_bounds__(2 * H) void k_deepset_bwd(const float* __restrict__ ens,
                                                        const uint16_t* __restrict__ mask,
@@ -844,17 +1002,39 @@ __global__ __launch_bounds__(2 * H) void k_deepset_bwd(const float* __restrict__
                                                        float* __restrict__ slab, int64_t N,
                                                        int M, int F, int num_groups) {
   __shared__ __attribute__((aligned(16))) float s_lds[ds_bwd_lds_floats<H, KP, G>()];
-#if GINE_DS_BWD_BF16X3
-  if (ds_bwd_body<H, KP, G, true>(ens, mask, dr, slab, N, M, F, num_groups, s_lds)) return;
-  __syncthreads();  // a non-finite operand: the fp32 form
-#endif
-  ds_bwd_body<H, KP, G, false>(ens, mask, dr, slab, N, M, F, num_groups, s_lds);
+  ds_bwd_kernel<H, KP, G, false>(ens, mask, dr, slab, N, M, F, num_groups, s_lds);
+}
+// The same at 16-node halves for a walk of full tiles only (FastStager)
+template <int H, int KP>
+__global__ __launch_bounds__(2 * H) void k_deepset_bwd_full(const float* __restrict__ ens,
+                                                            const uint16_t* __restrict__ mask,
+                                                            const float* __restrict__ dr,
+                                                            float* __restrict__ slab, int64_t N,
+                                                            int M, int F, int num_groups) {
+  __shared__ __attribute__((aligned(16))) float s_lds[ds_bwd_lds_floats<H, KP, 16>()];
+  ds_bwd_kernel<H, KP, 16, true>(ens, mask, dr, slab, N, M, F, num_groups, s_lds);
 }
 
 // The DeepSet backward with the dense chain's backward in front of it (G = 16, one group per
 // workgroup: gridDim.x == num_groups): each workgroup makes the dr of its own 32 nodes from
 // their dh0 rows (ds_chain_tile) while the walk's first tiles are in flight, instead of a
 // chain launch writing dr for this one to read back.  No workgroup waits for another.
+template <int H, int KP, bool FAST>
+__device__ __forceinline__ void ds_bwd_chain_kernel(const float* __restrict__ ens,
+                                                    const uint16_t* __restrict__ mask,
+                                                    const DsChainArgs& ch,
+                                                    float* __restrict__ slab, int64_t N, int M,
+                                                    int F, int num_groups, float* s_lds) {
+#if GINE_DS_BWD_BF16X3
+  if (ds_bwd_body<H, KP, 16, true, true, FAST>(ens, mask, nullptr, slab, N, M, F, num_groups,
+                                               s_lds, ch))
+    return;
+  __syncthreads();  // a non-finite operand: the fp32 form (the chain tile again: same values)
+#endif
+  ds_bwd_body<H, KP, 16, false, true, FAST>(ens, mask, nullptr, slab, N, M, F, num_groups, s_lds,
+                                            ch);
+}
+
 template <int H, int KP>
 __global__ __launch_bounds__(2 * H) void k_deepset_bwd_chain(const float* __restrict__ ens,
                                                              const uint16_t* __restrict__ mask,
@@ -863,13 +1043,16 @@ __global__ __launch_bounds__(2 * H) void k_deepset_bwd_chain(const float* __rest
                                                              int M, int F, int num_groups) {
   __shared__ __attribute__((aligned(16)))
   float s_lds[ds_bwd_lds_floats<H, KP, 16>() + ds_chain_lds_floats<H>()];
-#if GINE_DS_BWD_BF16X3
-  if (ds_bwd_body<H, KP, 16, true, true>(ens, mask, nullptr, slab, N, M, F, num_groups, s_lds,
-                                         ch))
-    return;
-  __syncthreads();  // a non-finite operand: the fp32 form (the chain tile again: same values)
-#endif
-  ds_bwd_body<H, KP, 16, false, true>(ens, mask, nullptr, slab, N, M, F, num_groups, s_lds, ch);
+  ds_bwd_chain_kernel<H, KP, false>(ens, mask, ch, slab, N, M, F, num_groups, s_lds);
+}
+// The same for a walk of full tiles only (FastStager)
+template <int H, int KP>
+__global__ __launch_bounds__(2 * H) void k_deepset_bwd_chain_full(
+    const float* __restrict__ ens, const uint16_t* __restrict__ mask, DsChainArgs ch,
+    float* __restrict__ slab, int64_t N, int M, int F, int num_groups) {
+  __shared__ __attribute__((aligned(16)))
+  float s_lds[ds_bwd_lds_floats<H, KP, 16>() + ds_chain_lds_floats<H>()];
+  ds_bwd_chain_kernel<H, KP, true>(ens, mask, ch, slab, N, M, F, num_groups, s_lds);
 }
 
 // 16 consecutive slab elements x 16 chunk groups per workgroup (many workgroups for the
@@ -898,7 +1081,7 @@ __global__ __launch_bounds__(256) void k_deepset_slab_reduce(const float* __rest
 }
 
 // forward: the MFMA k-split needs KP % 8 == 0; backward: rows stage as float4, KP % 4 == 0
-inline int pad_fwd(int F) {
+constexpr int pad_fwd(int F) {
   if (F <= 16) return 16;
   if (F <= 32) return 32;
   if (F <= 40) return 40;
@@ -906,7 +1089,7 @@ inline int pad_fwd(int F) {
   if (F <= 64) return 64;
   return -1;
 }
-inline int pad_bwd(int F) {
+constexpr int pad_bwd(int F) {
   if (F <= 16) return 16;
   if (F <= 32) return 32;
   if (F <= 36) return 36;
@@ -915,6 +1098,21 @@ inline int pad_bwd(int F) {
   if (F <= 64) return 64;
   return -1;
 }
+
+// ds_fmin is the inverse of the two functions above: FastStager sizes its float4 rounds by it,
+// and a value above the true lower bound would let a float4 read past the tile's 32*F floats
+template <bool BWD, int... KPS>
+constexpr bool ds_fmin_is_lower_bound() {
+  bool ok = true;
+  for (int kp : {KPS...}) {
+    const int f = ds_fmin(kp, BWD);
+    ok = ok && (BWD ? pad_bwd(f) : pad_fwd(f)) == kp &&
+         (f == 1 || (BWD ? pad_bwd(f - 1) : pad_fwd(f - 1)) < kp);
+  }
+  return ok;
+}
+static_assert(ds_fmin_is_lower_bound<false, 16, 32, 40, 48, 64>(), "ds_fmin vs pad_fwd");
+static_assert(ds_fmin_is_lower_bound<true, 16, 32, 36, 40, 48, 64>(), "ds_fmin vs pad_bwd");
 
 inline bool hidden_ok(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }
 
@@ -942,6 +1140,59 @@ inline int num_groups(int64_t N, int H) {
 // same slab bytes) workgroups; a smaller grid walks several groups per workgroup.
 inline int bwd_grid(int64_t N, int H) {
   return std::min(num_groups(N, H), H >= 128 ? 512 : 1024);
+}
+
+// gine_testing_deepset_generic_stager: nonzero keeps every launch on the generic stager (0 in
+// production), the in-tree reference of the fast one
+std::atomic<int> g_ds_generic{0};
+
+// The fast stager's conditions, uniform for a launch: every tile of every walk full (16-node
+// halves and only whole groups of 32 nodes; G*M*F is then a multiple of 4), ens on a 16-byte
+// boundary, and the hidden widths it is built for.  Anything else -- a short last group, the
+// padded rows of 8- and 4-node groups, an unaligned view -- runs the generic stager.
+inline bool ds_fast_ok(const float* ens, int64_t N, int G, int H) {
+  return g_ds_generic.load() == 0 && G == 16 && N > 0 && N % 32 == 0 && (H == 64 || H == 128) &&
+         (reinterpret_cast<uintptr_t>(ens) & 15) == 0;
+}
+
+// Launches: the full-tile kernels exist for 16-node halves at H = 64 / 128 only
+template <int H, int KP, int G, bool MK, bool FOLD>
+void launch_ds_fwd(bool fast, int grid, hipStream_t s, const float* ens, const float* w1,
+                   const float* b1, float* r, uint16_t* mask, int64_t N, int M, int F,
+                   int groups, const FoldArgs& fold, const Fold2Args& fold2) {
+  if constexpr (G == 16 && (H == 64 || H == 128)) {
+    if (fast) {
+      hipLaunchKernelGGL((k_deepset_fwd<H, KP, kFullTiles, MK, FOLD>), dim3(grid), dim3(2 * H), 0,
+                         s, ens, w1, b1, r, mask, N, M, F, groups, fold, fold2);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_deepset_fwd<H, KP, G, MK, FOLD>), dim3(grid), dim3(2 * H), 0, s,
+                     ens, w1, b1, r, mask, N, M, F, groups, fold, fold2);
+}
+template <int H, int KP, int G>
+void launch_ds_bwd(bool fast, int grid, hipStream_t s, const float* ens, const uint16_t* mask,
+                   const float* dr, float* slab, int64_t N, int M, int F, int groups) {
+  if constexpr (G == 16 && (H == 64 || H == 128)) {
+    if (fast) {
+      hipLaunchKernelGGL((k_deepset_bwd_full<H, KP>), dim3(grid), dim3(2 * H), 0, s, ens,
+                         mask, dr, slab, N, M, F, groups);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_deepset_bwd<H, KP, G>), dim3(grid), dim3(2 * H), 0, s, ens, mask,
+                     dr, slab, N, M, F, groups);
+}
+template <int H, int KP>
+void launch_ds_bwd_chain(bool fast, int groups, hipStream_t s, const float* ens,
+                         const uint16_t* mask, const DsChainArgs& ch, float* slab, int64_t N,
+                         int M, int F) {
+  if (fast)
+    hipLaunchKernelGGL((k_deepset_bwd_chain_full<H, KP>), dim3(groups), dim3(2 * H), 0, s, ens,
+                       mask, ch, slab, N, M, F, groups);
+  else
+    hipLaunchKernelGGL((k_deepset_bwd_chain<H, KP>), dim3(groups), dim3(2 * H), 0, s, ens,
+                       mask, ch, slab, N, M, F, groups);
 }
 
 #define DS_FWD_KP(H_, KP_, MACRO)                         \
@@ -993,6 +1244,18 @@ extern "C" int gine_deepset_mask_layout(int64_t num_nodes, int32_t hidden,
   return GINE_OK;
 }
 
+extern "C" int gine_testing_deepset_generic_stager(int32_t on) {
+  g_ds_generic.store(on != 0 ? 1 : 0);
+  return GINE_OK;
+}
+
+extern "C" int gine_testing_deepset_stager(const float* ens, int64_t num_nodes, int32_t hidden,
+                                           int32_t* full_tiles) {
+  if (!full_tiles || num_nodes < 0 || !hidden_ok(hidden)) return GINE_ERR_INVALID;
+  *full_tiles = ds_fast_ok(ens, num_nodes, nodes_per_half(num_nodes, hidden), hidden) ? 1 : 0;
+  return GINE_OK;
+}
+
 extern "C" int gine_deepset_fwd(const float* ens, const float* w1, const float* b1, float* r,
                                 uint16_t* mask, int64_t num_nodes, int32_t members,
                                 int32_t in_features, int32_t hidden, void* stream) {
@@ -1005,11 +1268,11 @@ extern "C" int gine_deepset_fwd(const float* ens, const float* w1, const float* 
   const int groups = num_groups(num_nodes, hidden);
   const int grid = std::min(groups, 1024);
   const int G = nodes_per_half(num_nodes, hidden);
+  const bool fast = ds_fast_ok(ens, num_nodes, G, hidden);
   hipStream_t s = as_stream(stream);
 #define LAUNCH_FWD_M(H_, KP_, G_, MK_)                                                        \
-  hipLaunchKernelGGL((k_deepset_fwd<H_, KP_, G_, MK_>), dim3(grid), dim3(2 * H_), 0, s, ens, w1, \
-                     b1, r, mask, num_nodes, members, in_features, groups, FoldArgs{},       \
-                     Fold2Args{})
+  launch_ds_fwd<H_, KP_, G_, MK_, false>(fast, grid, s, ens, w1, b1, r, mask, num_nodes,      \
+                                         members, in_features, groups, FoldArgs{}, Fold2Args{})
 #define LAUNCH_FWD_G(H_, KP_, G_)                             \
   do {                                                        \
     if (mask) LAUNCH_FWD_M(H_, KP_, G_, true);                \
@@ -1054,9 +1317,10 @@ extern "C" int gine_deepset_bwd(const float* ens, const uint16_t* mask, const fl
   if (num_nodes == 0) {
     GINE_RETURN_IF_HIP(hipMemsetAsync(slab, 0, sizeof(float) * per * grid, s));
   } else {
+    const bool fast = ds_fast_ok(ens, num_nodes, G, hidden);
 #define LAUNCH_BWD_G(H_, KP_, G_)                                                             \
-  hipLaunchKernelGGL((k_deepset_bwd<H_, KP_, G_>), dim3(grid), dim3(2 * H_), 0, s, ens, mask,  \
-                     dr, slab, num_nodes, members, in_features, groups)
+  launch_ds_bwd<H_, KP_, G_>(fast, grid, s, ens, mask, dr, slab, num_nodes, members,          \
+                             in_features, groups)
 #define LAUNCH_BWD(H_, KP_)                       \
   do {                                            \
     if (G == 4) LAUNCH_BWD_G(H_, KP_, 4);         \
@@ -1109,9 +1373,10 @@ extern "C" int gine_deepset_bwd_chain(const float* ens, const uint16_t* mask, co
   const int64_t per = (int64_t)hidden * in_features + hidden;
   const DsChainArgs ch{dh0, u, wfold, wfold2, dt, x_features};
   hipStream_t s = as_stream(stream);
+  const bool fast = ds_fast_ok(ens, num_nodes, 16, hidden);
 #define LAUNCH_BWD_C(H_, KP_)                                                                 \
-  hipLaunchKernelGGL((k_deepset_bwd_chain<H_, KP_>), dim3(groups), dim3(2 * H_), 0, s, ens,   \
-                     mask, ch, slab, num_nodes, members, in_features, groups)
+  launch_ds_bwd_chain<H_, KP_>(fast, groups, s, ens, mask, ch, slab, num_nodes, members,      \
+                               in_features)
   if (hidden == 64) {
     switch (KP) {  // (48: not eligible)
       case 16: LAUNCH_BWD_C(64, 16); break;
@@ -1184,11 +1449,11 @@ extern "C" int gine_deepset_fwd_fold2(const float* ens, const float* w1, const f
   const int walk = num_nodes > 0 ? std::min(groups, 1024) : 0;
   const int G = nodes_per_half(num_nodes, hidden);
   const int nfold = 2 * (hidden == 64 ? kFoldBlocks<64> : kFoldBlocks<128>);
+  const bool fast = ds_fast_ok(ens, num_nodes, G, hidden);
   hipStream_t s = as_stream(stream);
 #define LAUNCH_FWD_F(H_, KP_, G_, MK_)                                                        \
-  hipLaunchKernelGGL((k_deepset_fwd<H_, KP_, G_, MK_, true>), dim3(walk + nfold),             \
-                     dim3(2 * H_), 0, s, ens, w1, b1, r, mask, num_nodes, members, in_features, \
-                     groups, fold, fold2)
+  launch_ds_fwd<H_, KP_, G_, MK_, true>(fast, walk + nfold, s, ens, w1, b1, r, mask, num_nodes, \
+                                        members, in_features, groups, fold, fold2)
 #define LAUNCH_FWD_G(H_, KP_, G_)                             \
   do {                                                        \
     if (mask) LAUNCH_FWD_F(H_, KP_, G_, true);                \
